@@ -7,6 +7,13 @@ is generated on-device (synthetic, TPC-H spec shaped — see datagen/tpch.py)
 during setup; generation and planning are untimed, query execution is timed.
 
 Rank 0 prints exactly one JSON line with the whole-job metric.
+
+A plain run does only what that figure needs: set up, warm up, time the
+steps, print. `--full` adds everything else the benchmark reports (the
+per-query breakdown of the last timed step). `--dump-outputs DIR` writes what
+the last timed step returned, one float64 `.npy` per result column plus each
+query's row count; inputs are seeded, so two builds run with the same arguments can be compared output
+for output.
 """
 from __future__ import annotations
 
@@ -18,6 +25,74 @@ import time
 
 # reduce HBM fragmentation for the large transient intermediates
 os.environ.setdefault("PYTORCH_ALLOC_CONF", "expandable_segments:True")
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all dumped arrays together stay under 64 MB
+
+
+def _as_float(v):
+    """One result value as a float64: numbers as they are, NULL as NaN,
+    dates as day ordinals, strings (and anything nested) as the CRC-32 of
+    their text, so that two builds can be compared value for value."""
+    import datetime
+    import zlib
+
+    if v is None:
+        return float("nan")
+    if isinstance(v, (bool, int, float)):
+        return float(v)
+    if isinstance(v, datetime.datetime):
+        return v.replace(tzinfo=v.tzinfo or datetime.timezone.utc).timestamp()
+    if isinstance(v, datetime.date):
+        return float(v.toordinal())
+    if isinstance(v, datetime.time):
+        return v.hour * 3600.0 + v.minute * 60.0 + v.second + v.microsecond * 1e-6
+    if isinstance(v, str):
+        return float(zlib.crc32(v.encode("utf-8")))
+    if isinstance(v, (bytes, bytearray)):
+        return float(zlib.crc32(bytes(v)))
+    try:
+        return float(v)  # decimal.Decimal, numpy scalars
+    except (TypeError, ValueError):
+        return float(zlib.crc32(repr(v).encode("utf-8")))
+
+
+def dump_outputs(results, out_dir):
+    """Write every result column of every query in `results` ({query id:
+    Chunk}, rows in the order the caller received them) as float64
+    `<out_dir>/q<id>_c<pos>_<column>.npy`, and the number of rows each query
+    returned as `q<id>_rows.npy`. A query that returned no rows (q11 at large
+    scale factors, whose HAVING fraction is fixed) leaves only that count: an
+    empty array holds nothing to compare. Outputs too large for the budget
+    are cut to a fixed, seeded sample of rows (the same rows for every column
+    of a query, in their original order)."""
+    import re
+
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n_arrays = sum(len(c.columns) for c in results.values())
+    max_rows = max(DUMP_BUDGET_BYTES // 8 // max(n_arrays, 1), 1)
+    for q in sorted(results):
+        chunk = results[q]
+        n = chunk.num_rows
+        np.save(os.path.join(out_dir, f"q{q:02d}_rows.npy"),
+                np.array([n], dtype=np.float64))
+        if n == 0:
+            continue
+        pick = None
+        if n > max_rows:
+            pick = np.sort(np.random.default_rng(q).choice(n, max_rows, replace=False))
+            pick = torch.from_numpy(pick).to(chunk.device)
+        for pos, (name, col) in enumerate(zip(chunk.names, chunk.columns)):
+            if col is None:  # slot the plan never referenced
+                continue
+            if pick is not None:
+                col = col.gather(pick)
+            arr = np.array([_as_float(v) for v in col.to_pylist()], dtype=np.float64)
+            safe = re.sub(r"[^0-9A-Za-z_]+", "_", str(name)).strip("_")[:40]
+            np.save(os.path.join(out_dir, f"q{q:02d}_c{pos:02d}_{safe}.npy"), arr)
 
 
 def main():
@@ -35,7 +110,17 @@ def main():
                     choices=["parquet", "resident"],
                     help="parquet: timed steps scan+GPU-decode parquet from disk "
                          "(BASELINE config #2); resident: HBM-resident tables")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the result columns of "
+                         "every query of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the per-query "
+                         "breakdown of the last timed step (implies --print-times)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.full:
+        args.print_times = True
 
     import torch
 
@@ -152,6 +237,9 @@ def main():
 
     progress = os.environ.get("SAIL_BENCH_PROGRESS") == "1"
 
+    # result chunks of the most recent step, kept only for --dump-outputs
+    last_results = {} if args.dump_outputs else None
+
     def one_step(collect_times=False):
         times = {}
         for q in qids:
@@ -168,12 +256,16 @@ def main():
             if use_cuda:
                 torch.cuda.synchronize()
             times[q] = time.time() - tq
+            if last_results is not None:
+                last_results[q] = chunk
         return times
 
+    t_warm = time.time()
     for _ in range(args.warmup):
         one_step()
 
     barrier_sync()
+    warm_s = time.time() - t_warm
     t0 = time.time()
     qtimes = None
     for _ in range(args.steps):
@@ -189,11 +281,14 @@ def main():
         elapsed = float(te.item())
 
     per_step = elapsed / args.steps
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last_results, args.dump_outputs)
     if rank == 0:
         if args.print_times and qtimes:
             for q in qids:
                 print(f"# q{q}: {qtimes[q]*1000:.1f} ms", file=sys.stderr)
-        print(f"# datagen: {gen_s:.1f}s, rows/GPU: {total_rows // max(world,1)}", file=sys.stderr)
+        print(f"# datagen: {gen_s:.1f}s, warmup: {warm_s:.1f}s, "
+              f"rows/GPU: {total_rows // max(world,1)}", file=sys.stderr)
         if args.workload == "clickbench":
             baseline = None
             metric = f"clickbench_{args.rows//1_000_000}m_total_s"
@@ -230,6 +325,8 @@ def main():
                 "parquet_bytes": scan_info["bytes"] if scan_info else None,
             },
         }
+        if args.full:
+            out["per_query_ms"] = {str(q): round(qtimes[q] * 1000, 2) for q in qids}
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

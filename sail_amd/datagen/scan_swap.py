@@ -6,7 +6,6 @@ and survive the swap (the analogue of the reference's statistics cache)."""
 from __future__ import annotations
 
 import os
-import tempfile
 from typing import Dict, Optional
 
 from ..engine.column import Table
@@ -29,9 +28,9 @@ def persist_and_swap(session, tables: Dict[str, Table], *,
 
         sync_table_stats(session)
     if data_dir is None:
-        data_dir = os.environ.get(
-            "SAIL_BENCH_DATA_DIR",
-            os.path.join(tempfile.gettempdir(), default_dir))
+        from ..utils.tmpdir import user_tmp
+
+        data_dir = os.environ.get("SAIL_BENCH_DATA_DIR", user_tmp(default_dir))
     paths = write_fn(tables, data_dir, rank)
     total_bytes = sum(os.path.getsize(p) for p in paths.values())
     for name, tbl in tables.items():

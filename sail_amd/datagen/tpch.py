@@ -444,6 +444,24 @@ def register_tpch(session, sf: float = 0.01, device=None, rank: int = 0, world: 
 # HBM"; ref: crates/sail-data-source/src/formats/parquet writer options).
 # ===========================================================================
 
+def _host_pinned(c: Column) -> Column:
+    """Device column -> host column through page-locked memory; a copy into
+    pageable memory moves at a fraction of the link's speed."""
+    def h(t):
+        if t is None or not t.is_cuda:
+            return t
+        out = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+        out.copy_(t)
+        return out
+
+    if isinstance(c, StringColumn):
+        return StringColumn(h(c.offsets), h(c.bytes_), h(c.validity), h(c.codes),
+                            dtype=c.dtype)
+    if type(c) is Column:
+        return Column(c.dtype, h(c.data), h(c.validity))
+    return c
+
+
 def write_tpch_parquet(tables: Dict[str, Table], out_dir: str, rank: int = 0,
                        row_group_rows: int = 1 << 20,
                        page_size: int = 1 << 20,
@@ -453,14 +471,19 @@ def write_tpch_parquet(tables: Dict[str, Table], out_dir: str, rank: int = 0,
     for raw strings (fully parallel decode), DELTA_BINARY_PACKED for
     ints/dates (small-range deltas bit-pack tightly), PLAIN/FLBA otherwise.
     Returns {table: path}. Existing files with matching sizes are reused."""
+    import functools
+
+    import pyarrow as pa
     import pyarrow.parquet as pq
 
     from ..datasource.arrow_io import chunk_to_arrow
     from ..engine.chunk import Chunk
     from ..engine.column import StringColumn
+    from .parquet_shards import write_files
 
     os.makedirs(out_dir, exist_ok=True)
     paths = {}
+    jobs, finished = [], []
     for name, tbl in tables.items():
         path = os.path.join(out_dir, f"{name}-r{rank:03d}.parquet")
         paths[name] = path
@@ -486,33 +509,41 @@ def write_tpch_parquet(tables: Dict[str, Table], out_dir: str, rank: int = 0,
                 # bytes on the wire and a plain int64 decode on the GPU
                 col_enc[n] = "DELTA_BINARY_PACKED"
         n = tbl.num_rows
-        writer = None
-        try:
-            for lo in range(0, max(n, 1), row_group_rows):
-                ln = min(row_group_rows, n - lo)
-                sub = Chunk([c.slice(lo, ln) for c in tbl.columns.values()],
-                            [cn for cn in tbl.columns])
-                at = chunk_to_arrow(sub, schema)
-                if writer is None:
-                    writer = pq.ParquetWriter(
-                        path, at.schema, compression=compression,
-                        use_dictionary=use_dict or False,
-                        column_encoding=col_enc or None,
-                        data_page_size=page_size,
-                        store_decimal_as_integer=True,
-                        # keep big dictionaries dict-encoded (ClickBench
-                        # URL/Title): a PLAIN fallback mid-chunk would push
-                        # the column to the host decode path
-                        dictionary_pagesize_limit=64 << 20,
-                        data_page_version="1.0")
+
+        def encode(lo, tbl=tbl, schema=schema, use_dict=use_dict,
+                   col_enc=col_enc, n=n):
+            """Rows [lo, lo+row_group_rows) as one single-row-group file."""
+            ln = min(row_group_rows, n - lo)
+            sub = Chunk([_host_pinned(c.slice(lo, ln)) for c in tbl.columns.values()],
+                        [cn for cn in tbl.columns])
+            at = chunk_to_arrow(sub, schema)
+            sink = pa.BufferOutputStream()
+            writer = pq.ParquetWriter(
+                sink, at.schema, compression=compression,
+                use_dictionary=use_dict or False,
+                column_encoding=col_enc or None,
+                data_page_size=page_size,
+                store_decimal_as_integer=True,
+                # keep big dictionaries dict-encoded (ClickBench
+                # URL/Title): a PLAIN fallback mid-chunk would push
+                # the column to the host decode path
+                dictionary_pagesize_limit=64 << 20,
+                data_page_version="1.0")
+            try:
                 writer.write_table(at, row_group_size=row_group_rows)
-                if n == 0:
-                    break
-        finally:
-            if writer is not None:
+            finally:
                 writer.close()
+            return sink.getvalue()
+
+        jobs.append((path, [functools.partial(encode, lo)
+                            for lo in range(0, max(n, 1), row_group_rows)]))
+        finished.append((done, tbl.num_rows))
+    # row groups are encoded on worker threads and stitched in order: the
+    # files are byte-identical to a single sequential ParquetWriter's
+    write_files(jobs)
+    for done, num_rows in finished:
         with open(done, "w") as f:
-            f.write(str(tbl.num_rows))
+            f.write(str(num_rows))
     return paths
 
 

@@ -120,7 +120,13 @@ class FileIndex:
             raise Unsupported(f"nested column {sc.name}")
         max_def = sc.max_definition_level
         out = []
-        with open(self.path, "rb") as f:
+        import mmap
+
+        # mapped, not read: only the pages holding headers and def levels
+        # are touched, not the gigabytes of values between them
+        with open(self.path, "rb") as f, \
+                mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm, \
+                memoryview(mm) as whole:
             for rg in range(self.meta.num_row_groups):
                 cmd = self.meta.row_group(rg).column(ci)
                 if cmd.compression != "UNCOMPRESSED":
@@ -130,48 +136,47 @@ class FileIndex:
                             if cmd.dictionary_page_offset is not None
                             else cmd.data_page_offset)
                 ch.end = ch.start + cmd.total_compressed_size
-                f.seek(ch.start)
-                raw = f.read(cmd.total_compressed_size)
-                pos = 0
-                while pos < len(raw):
-                    hdr, dpos = tc.parse_page_header(raw, pos)
-                    ptype = hdr[tc.PAGE_TYPE]
-                    csz = hdr[tc.COMPRESSED_SIZE]
-                    if ptype == 2:  # dictionary page
-                        dph = hdr.get(tc.DICT_PAGE_HEADER, {})
-                        if dph.get(tc.DICT_ENCODING, PLAIN) not in (
-                                PLAIN, PLAIN_DICTIONARY):
-                            raise Unsupported(f"{sc.name}: dict page encoding")
-                        ch.dict_off = ch.start + dpos
-                        ch.dict_len = csz
-                        ch.dict_nvals = dph.get(tc.DICT_NUM_VALUES, 0)
-                    elif ptype == 0:  # data page v1
-                        dph = hdr.get(tc.DATA_PAGE_HEADER, {})
-                        nvals = dph.get(tc.DPH_NUM_VALUES, 0)
-                        enc = dph.get(tc.DPH_ENCODING, PLAIN)
-                        if enc == PLAIN_DICTIONARY:
-                            enc = RLE_DICTIONARY
-                        body = dpos
-                        if max_def > 0:
-                            if dph.get(tc.DPH_DEF_ENCODING, RLE) != RLE:
-                                raise Unsupported(f"{sc.name}: def-level encoding")
-                            dl = int.from_bytes(raw[body:body + 4], "little")
-                            def_off = ch.start + body + 4
-                            def_len = dl
-                            av = _check_all_valid(raw, body + 4, dl, nvals)
-                            body += 4 + dl
+                with whole[ch.start:ch.end] as raw:
+                    pos = 0
+                    while pos < len(raw):
+                        hdr, dpos = tc.parse_page_header(raw, pos)
+                        ptype = hdr[tc.PAGE_TYPE]
+                        csz = hdr[tc.COMPRESSED_SIZE]
+                        if ptype == 2:  # dictionary page
+                            dph = hdr.get(tc.DICT_PAGE_HEADER, {})
+                            if dph.get(tc.DICT_ENCODING, PLAIN) not in (
+                                    PLAIN, PLAIN_DICTIONARY):
+                                raise Unsupported(f"{sc.name}: dict page encoding")
+                            ch.dict_off = ch.start + dpos
+                            ch.dict_len = csz
+                            ch.dict_nvals = dph.get(tc.DICT_NUM_VALUES, 0)
+                        elif ptype == 0:  # data page v1
+                            dph = hdr.get(tc.DATA_PAGE_HEADER, {})
+                            nvals = dph.get(tc.DPH_NUM_VALUES, 0)
+                            enc = dph.get(tc.DPH_ENCODING, PLAIN)
+                            if enc == PLAIN_DICTIONARY:
+                                enc = RLE_DICTIONARY
+                            body = dpos
+                            if max_def > 0:
+                                if dph.get(tc.DPH_DEF_ENCODING, RLE) != RLE:
+                                    raise Unsupported(f"{sc.name}: def-level encoding")
+                                dl = int.from_bytes(raw[body:body + 4], "little")
+                                def_off = ch.start + body + 4
+                                def_len = dl
+                                av = _check_all_valid(raw, body + 4, dl, nvals)
+                                body += 4 + dl
+                            else:
+                                def_off, def_len, av = 0, 0, True
+                            val_off = ch.start + body
+                            val_len = csz - (body - dpos)
+                            bw0 = raw[body] if (enc == RLE_DICTIONARY
+                                                and body < len(raw)) else 0
+                            ch.pages.append(
+                                _Page(nvals, enc, def_off, def_len, val_off,
+                                      val_len, av, bw0))
                         else:
-                            def_off, def_len, av = 0, 0, True
-                        val_off = ch.start + body
-                        val_len = csz - (body - dpos)
-                        bw0 = raw[body] if (enc == RLE_DICTIONARY
-                                            and body < len(raw)) else 0
-                        ch.pages.append(
-                            _Page(nvals, enc, def_off, def_len, val_off,
-                                  val_len, av, bw0))
-                    else:
-                        raise Unsupported(f"{sc.name}: page type {ptype}")
-                    pos = dpos + csz
+                            raise Unsupported(f"{sc.name}: page type {ptype}")
+                        pos = dpos + csz
                 out.append(ch)
         self._chunks[ci] = out
         return out

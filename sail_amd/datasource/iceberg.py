@@ -207,8 +207,10 @@ class IcebergTable:
             ts = int(ts)
             best = None
             for s in snaps:
+                # >=: snapshots committed within one millisecond tie, and
+                # the later one in commit order is the state at that time
                 if s["timestamp-ms"] <= ts and (
-                        best is None or s["timestamp-ms"] > best["timestamp-ms"]):
+                        best is None or s["timestamp-ms"] >= best["timestamp-ms"]):
                     best = s
             if best is None:
                 raise ValueError(f"no Iceberg snapshot at or before {ts}")

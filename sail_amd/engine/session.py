@@ -757,7 +757,9 @@ class DataFrame:
 
         root = self.session.conf.get("sail.execution.checkpoint_path")
         if not root:
-            root = os.path.join(tempfile.gettempdir(), "sail_checkpoints")
+            from ..utils.tmpdir import user_tmp
+
+            root = user_tmp("sail_checkpoints")
         path = os.path.join(root, _uuid.uuid4().hex)
         if not eager:
             # lazy checkpoint: materialize on first use; for this engine's

@@ -56,10 +56,11 @@ class ObjectStore:
     def as_local(self, path: str) -> str:
         """Local filesystem path holding this object (staged if remote)."""
         import hashlib
-        import tempfile
+
+        from ..utils.tmpdir import user_tmp
 
         key = hashlib.sha1(path.encode()).hexdigest()[:16]
-        target = os.path.join(tempfile.gettempdir(), "sail_store_cache",
+        target = os.path.join(user_tmp("sail_store_cache"),
                               f"{key}-{os.path.basename(path)}")
         os.makedirs(os.path.dirname(target), exist_ok=True)
         # always restage: the object may have been overwritten since the

@@ -131,6 +131,126 @@ def read_struct(buf: bytes, pos: int, parse: bool = True) -> Tuple[Dict[int, obj
     raise AssertionError  # unreachable
 
 
+# -- lossless tree form (read + re-emit) --------------------------------------
+# A struct is a list of [field_id, wire_type, value]; value is an int for the
+# integer types, bytes for binary/double, (elem_type, [values]) for lists and
+# sets, a nested struct list for structs, None for booleans (the wire type
+# carries them). Used to rewrite parquet footers (datagen/parquet_shards.py).
+
+def _read_value(buf, pos: int, wtype: int):
+    if wtype in (CT_TRUE, CT_FALSE):
+        return None, pos
+    if wtype == CT_BYTE:
+        return buf[pos], pos + 1
+    if wtype in (CT_I16, CT_I32, CT_I64):
+        raw, pos = _varint(buf, pos)
+        return _zigzag(raw), pos
+    if wtype == CT_DOUBLE:
+        return bytes(buf[pos:pos + 8]), pos + 8
+    if wtype == CT_BINARY:
+        n, pos = _varint(buf, pos)
+        return bytes(buf[pos:pos + n]), pos + n
+    if wtype in (CT_LIST, CT_SET):
+        head = buf[pos]
+        pos += 1
+        n = head >> 4
+        et = head & 0x0F
+        if n == 15:
+            n, pos = _varint(buf, pos)
+        vals = []
+        for _ in range(n):
+            if et in (CT_TRUE, CT_FALSE):  # list<bool>: one byte per element
+                vals.append(buf[pos])
+                pos += 1
+            else:
+                v, pos = _read_value(buf, pos, et)
+                vals.append(v)
+        return (et, vals), pos
+    if wtype == CT_STRUCT:
+        return read_tree(buf, pos)
+    raise ValueError(f"thrift compact: unsupported wire type {wtype}")
+
+
+def read_tree(buf, pos: int = 0):
+    """Parse one struct into the lossless tree form; returns (tree, end_pos)."""
+    out = []
+    fid = 0
+    while True:
+        head = buf[pos]
+        pos += 1
+        if head == CT_STOP:
+            return out, pos
+        delta = head >> 4
+        wtype = head & 0x0F
+        if delta:
+            fid += delta
+        else:
+            raw, pos = _varint(buf, pos)
+            fid = _zigzag(raw)
+        val, pos = _read_value(buf, pos, wtype)
+        out.append([fid, wtype, val])
+
+
+def _put_varint(out: bytearray, v: int) -> None:
+    while v >= 0x80:
+        out.append((v & 0x7F) | 0x80)
+        v >>= 7
+    out.append(v)
+
+
+def _put_zigzag(out: bytearray, v: int) -> None:
+    _put_varint(out, (v << 1) if v >= 0 else ((-v << 1) - 1))
+
+
+def _write_value(out: bytearray, wtype: int, val) -> None:
+    if wtype in (CT_TRUE, CT_FALSE):
+        return
+    if wtype == CT_BYTE:
+        out.append(val)
+    elif wtype in (CT_I16, CT_I32, CT_I64):
+        _put_zigzag(out, val)
+    elif wtype == CT_DOUBLE:
+        out += val
+    elif wtype == CT_BINARY:
+        _put_varint(out, len(val))
+        out += val
+    elif wtype in (CT_LIST, CT_SET):
+        et, vals = val
+        if len(vals) < 15:
+            out.append((len(vals) << 4) | et)
+        else:
+            out.append(0xF0 | et)
+            _put_varint(out, len(vals))
+        for v in vals:
+            if et in (CT_TRUE, CT_FALSE):
+                out.append(v)
+            else:
+                _write_value(out, et, v)
+    elif wtype == CT_STRUCT:
+        write_tree(val, out)
+    else:
+        raise ValueError(f"thrift compact: unsupported wire type {wtype}")
+
+
+def write_tree(tree, out: bytearray = None) -> bytearray:
+    """Serialize a tree from read_tree(); an unmodified tree re-emits the
+    bytes it was parsed from (canonical short-form field headers)."""
+    if out is None:
+        out = bytearray()
+    last = 0
+    for fid, wtype, val in tree:
+        delta = fid - last
+        if 0 < delta <= 15:
+            out.append((delta << 4) | wtype)
+        else:
+            out.append(wtype)
+            _put_zigzag(out, fid)
+        _write_value(out, wtype, val)
+        last = fid
+    out.append(CT_STOP)
+    return out
+
+
 # PageHeader field ids (parquet.thrift)
 PAGE_TYPE = 1            # 0=DATA_PAGE 2=DICTIONARY_PAGE 3=DATA_PAGE_V2
 UNCOMPRESSED_SIZE = 2

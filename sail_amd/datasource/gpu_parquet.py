@@ -362,7 +362,9 @@ def _page_table(rows, device):
 def _segmented_cumsum(deltas: torch.Tensor, counts: List[int]) -> torch.Tensor:
     """Per-page cumulative sum: deltas holds [first, d1, ...] per segment."""
     cs = torch.cumsum(deltas, 0)
-    if len(counts) <= 1:
+    # no values at all (every page null): the base gather below would index
+    # an empty tensor
+    if len(counts) <= 1 or deltas.numel() == 0:
         return cs
     bounds = np.cumsum([0] + counts[:-1])
     starts = torch.from_numpy(bounds).to(deltas.device)
@@ -588,11 +590,13 @@ class _ColumnDecoder:
 
     def _decode_dict_codes(self, ext, dict_rows):
         """RLE_DICTIONARY pages: first byte = bitwidth (captured at index
-        time), then hybrid runs. Decodes codes densely in dict_rows order."""
+        time), then hybrid runs. Decodes codes densely in dict_rows order.
+        Width 0 is legal (one-entry dictionary under parquet-mr/arrow-rs):
+        RLE runs then carry no value bytes, so it must not be clamped."""
         rows = []
         at = 0
         for r in dict_rows:
-            rows.append((r[0] + 1, r[1] - 1, r[2], at, 0, max(int(r[5]), 1)))
+            rows.append((r[0] + 1, r[1] - 1, r[2], at, 0, int(r[5])))
             at += r[2]
         return _ext().pq_rle_decode(self.buf, _page_table(rows, self.device), at)
 

@@ -30,6 +30,14 @@ constexpr int kBlock = 256;   // 4 wave64
 constexpr int kRuns = 512;    // LDS run-table entries per batch
 
 // Page descriptor: int64 [n,6] = {src_off, src_len, n_values, out_row, aux, bw}
+//
+// Buffer contract: `buf` is 4-byte aligned and extends at least 16 bytes past
+// the end of the last page (the staging upload is total + 16 bytes).
+// plain_copy_kernel and copy_bytes_kernel load whole aligned dwords, so they
+// read the aligned dword that holds a page's last source byte, i.e. up to 3
+// bytes before src_off and up to 3 bytes past src_off + src_len. Those bytes
+// are read but never reach the output. A page with n_values == 0 writes
+// nothing to any value output; delta_decode_kernel still writes data_end[p].
 struct PageView {
   const uint8_t* src;
   long len;
@@ -265,7 +273,10 @@ __global__ void delta_decode_kernel(const uint8_t* __restrict__ buf,
       long mbpb = (long)read_varint(pg.src, pos);
       long total = (long)read_varint(pg.src, pos);
       long first = zigzag(read_varint(pg.src, pos));
-      dst[0] = first;
+      // a page with no non-null values owns no output slot: its out_row is
+      // the next page's (or one past the end), so the store is predicated.
+      // data_end[p] below is still the position just after the header.
+      if (pg.nvals > 0) dst[0] = first;
       s_pos = pos;
       s_didx = 0;
       s_vpm = (int)(block_size / mbpb);

@@ -2,8 +2,10 @@
 
 Implements the exact kernel contracts (page-descriptor tables, dense
 outputs) so the host orchestration in datasource/gpu_parquet.py can be
-validated on CPU; the HIP kernels themselves are checked against pyarrow
-on the GPU (tests/test_gpu.py)."""
+validated on CPU. tests/test_pq_kernels.py checks both this simulator (CPU)
+and the HIP kernels (GPU) against encoder ground truth from
+tests/pq_encode.py; tests/test_gpu.py checks the kernels end-to-end against
+pyarrow."""
 from __future__ import annotations
 
 import numpy as np
@@ -35,6 +37,13 @@ def _wrap64(v):
     return v - (1 << 64) if v >= (1 << 63) else v
 
 
+def _wrap32(v):
+    """Bit pattern of the kernel's (int) cast: width-32 values with the top
+    bit set come out negative."""
+    v = int(v) & 0xFFFFFFFF
+    return v - (1 << 32) if v >= (1 << 31) else v
+
+
 def _read_bits(buf, bit, bw):
     byte = bit >> 3
     sh = bit & 7
@@ -62,7 +71,8 @@ def pq_rle_decode(buf_t, pages_t, total):
                 groups = h >> 1
                 cnt = min(groups * 8, nvals - v)
                 for i in range(cnt):
-                    out[out_row + v + i] = _read_bits(src, (pos * 8) + i * bw, bw)
+                    out[out_row + v + i] = _wrap32(
+                        _read_bits(src, (pos * 8) + i * bw, bw))
                 pos += groups * bw
             else:
                 cnt = min(h >> 1, nvals - v)
@@ -71,7 +81,7 @@ def pq_rle_decode(buf_t, pages_t, total):
                 for i in range(nb):
                     val |= int(src[pos + i]) << (8 * i)
                 pos += nb
-                out[out_row + v:out_row + v + cnt] = val
+                out[out_row + v:out_row + v + cnt] = _wrap32(val)
             v += cnt
     return torch.from_numpy(out)
 
@@ -119,7 +129,8 @@ def pq_delta_decode(buf_t, pages_t, total):
         mbpb, pos = _read_varint(src, pos)
         tot, pos = _read_varint(src, pos)
         first_raw, pos = _read_varint(src, pos)
-        out[out_row] = _wrap64(_zigzag(first_raw))
+        if nvals > 0:  # an empty page owns no output slot
+            out[out_row] = _wrap64(_zigzag(first_raw))
         vpm = block_size // mbpb
         n = min(tot, nvals)
         ndeltas = max(n - 1, 0)

@@ -27,6 +27,10 @@ DEFAULTS: Dict[str, str] = {
     # auto = GPU decode when supported, host pyarrow otherwise;
     # force = raise instead of falling back (tests); off = host only
     "sail.io.gpu_parquet": "auto",
+    # opt-in: decompress SNAPPY parquet pages on the GPU (ops/csrc/snappy.hip)
+    # instead of sending the file to the host path; on | off
+    # (env SAIL_IO_GPU_SNAPPY, read option gpuSnappy)
+    "sail.io.gpu_snappy": "off",
     # kernels
     "sail.kernels.require_on_gpu": "true",
     "sail.kernels.grouped_agg_max_lds_groups": "4096",

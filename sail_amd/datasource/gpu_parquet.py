@@ -13,6 +13,18 @@ byte_array, RLE_DICTIONARY (+PLAIN dictionary pages), DELTA_BINARY_PACKED,
 DELTA_LENGTH_BYTE_ARRAY, FLBA/INT32/INT64 decimals, definition levels
 (nulls). Anything else raises Unsupported and the caller falls back to the
 host pyarrow path (parquet_io.read).
+
+Opt-in (config sail.io.gpu_snappy / env SAIL_IO_GPU_SNAPPY / read option
+gpuSnappy, default off): SNAPPY column chunks with v1 data pages. The
+compressed chunk bytes are uploaded as they are, one launch of
+pq_snappy_decompress (ops/csrc/snappy.hip) expands every page of the
+window, dictionary pages included, into a packed device buffer, and the
+page decoders above run on that buffer. In a compressed page the
+definition levels and the dictionary bit-width byte are inside the
+compressed body, so they are resolved after the first decompress of a
+column from two small device->host gathers and cached on the page index.
+A page the kernel rejects (non-zero status) raises Unsupported. Other
+codecs, v2 data pages and pages of 2^31 bytes or more stay on the host path.
 """
 from __future__ import annotations
 
@@ -35,16 +47,38 @@ DELTA_LENGTH_BYTE_ARRAY = 6
 RLE_DICTIONARY = 8
 
 
+_MAX_PAGE = 1 << 31   # pq_snappy_decompress takes lengths below 2^31
+
+
 class Unsupported(Exception):
     """Feature outside the GPU decoder; caller falls back to host decode."""
 
 
+def snappy_enabled(options=None) -> bool:
+    """The opt-in switch for device Snappy decompression: read option
+    `gpuSnappy`, else env SAIL_IO_GPU_SNAPPY (config sail.io.gpu_snappy);
+    default off."""
+    if options and options.get("gpuSnappy") is not None:
+        v = options["gpuSnappy"]
+    else:
+        v = os.environ.get("SAIL_IO_GPU_SNAPPY", "off")
+    return str(v).lower() in ("on", "true", "1")
+
+
 class _Page:
+    """One data page. Uncompressed: def_off/val_off are absolute file
+    offsets, known at index time. Compressed: comp_off/comp_len is the
+    compressed body in the file, ulen its uncompressed length, and
+    def_off/val_off are relative to the start of the decompressed body;
+    they, def_len, val_len, all_valid and bw0 are filled in on the first
+    decode (`resolved`)."""
+
     __slots__ = ("nvals", "enc", "def_off", "def_len", "val_off", "val_len",
-                 "all_valid", "bw0")
+                 "all_valid", "bw0", "comp_off", "comp_len", "ulen",
+                 "resolved")
 
     def __init__(self, nvals, enc, def_off, def_len, val_off, val_len,
-                 all_valid, bw0=0):
+                 all_valid, bw0=0, comp_off=None, comp_len=0, ulen=0):
         self.nvals = nvals
         self.enc = enc
         self.def_off = def_off    # absolute file offset of RLE def runs
@@ -53,10 +87,15 @@ class _Page:
         self.val_len = val_len
         self.all_valid = all_valid
         self.bw0 = bw0            # RLE_DICTIONARY: leading bit-width byte
+        self.comp_off = comp_off  # compressed page: absolute file offset
+        self.comp_len = comp_len
+        self.ulen = ulen
+        self.resolved = comp_off is None
 
 
 class _Chunk:
-    __slots__ = ("start", "end", "pages", "dict_off", "dict_len", "dict_nvals")
+    __slots__ = ("start", "end", "pages", "dict_off", "dict_len", "dict_nvals",
+                 "compressed", "dict_ulen")
 
     def __init__(self):
         self.start = 0
@@ -65,6 +104,8 @@ class _Chunk:
         self.dict_off = None
         self.dict_len = 0
         self.dict_nvals = 0
+        self.compressed = False   # SNAPPY: dict_off/dict_len are compressed
+        self.dict_ulen = 0        # ... and this is the dictionary's length
 
 
 def _check_all_valid(raw: bytes, pos: int, length: int, nvals: int) -> bool:
@@ -105,16 +146,21 @@ class FileIndex:
         self.num_rows = self.meta.num_rows
         self._cols: Dict[str, int] = {
             self.schema.column(i).name: i for i in range(len(self.schema))}
-        self._chunks: Dict[int, List[_Chunk]] = {}
+        # keyed by (column, snappy switch): an index built with the switch
+        # off must not answer for one built with it on
+        self._chunks: Dict[Tuple[int, bool], List[_Chunk]] = {}
 
     def column_index(self, name: str) -> int:
         if name not in self._cols:
             raise Unsupported(f"column {name} not in {self.path}")
         return self._cols[name]
 
-    def chunks(self, ci: int) -> List[_Chunk]:
-        if ci in self._chunks:
-            return self._chunks[ci]
+    def chunks(self, ci: int, snappy: Optional[bool] = None) -> List[_Chunk]:
+        """Page tables of column `ci`. `snappy` accepts SNAPPY chunks
+        (None: the SAIL_IO_GPU_SNAPPY environment switch)."""
+        snappy = snappy_enabled() if snappy is None else bool(snappy)
+        if (ci, snappy) in self._chunks:
+            return self._chunks[(ci, snappy)]
         sc = self.schema.column(ci)
         if sc.max_repetition_level > 0:
             raise Unsupported(f"nested column {sc.name}")
@@ -129,9 +175,11 @@ class FileIndex:
                 memoryview(mm) as whole:
             for rg in range(self.meta.num_row_groups):
                 cmd = self.meta.row_group(rg).column(ci)
-                if cmd.compression != "UNCOMPRESSED":
+                comp = cmd.compression != "UNCOMPRESSED"
+                if comp and not (snappy and cmd.compression == "SNAPPY"):
                     raise Unsupported(f"{sc.name}: compression {cmd.compression}")
                 ch = _Chunk()
+                ch.compressed = comp
                 ch.start = (cmd.dictionary_page_offset
                             if cmd.dictionary_page_offset is not None
                             else cmd.data_page_offset)
@@ -142,6 +190,11 @@ class FileIndex:
                         hdr, dpos = tc.parse_page_header(raw, pos)
                         ptype = hdr[tc.PAGE_TYPE]
                         csz = hdr[tc.COMPRESSED_SIZE]
+                        usz = hdr.get(tc.UNCOMPRESSED_SIZE, csz)
+                        if comp and not (0 <= csz < _MAX_PAGE
+                                         and 0 <= usz < _MAX_PAGE):
+                            raise Unsupported(f"{sc.name}: page of 2^31 bytes "
+                                              "or more")
                         if ptype == 2:  # dictionary page
                             dph = hdr.get(tc.DICT_PAGE_HEADER, {})
                             if dph.get(tc.DICT_ENCODING, PLAIN) not in (
@@ -149,6 +202,7 @@ class FileIndex:
                                 raise Unsupported(f"{sc.name}: dict page encoding")
                             ch.dict_off = ch.start + dpos
                             ch.dict_len = csz
+                            ch.dict_ulen = usz
                             ch.dict_nvals = dph.get(tc.DICT_NUM_VALUES, 0)
                         elif ptype == 0:  # data page v1
                             dph = hdr.get(tc.DATA_PAGE_HEADER, {})
@@ -157,9 +211,19 @@ class FileIndex:
                             if enc == PLAIN_DICTIONARY:
                                 enc = RLE_DICTIONARY
                             body = dpos
+                            if max_def > 0 and \
+                                    dph.get(tc.DPH_DEF_ENCODING, RLE) != RLE:
+                                raise Unsupported(f"{sc.name}: def-level encoding")
+                            if comp:
+                                # levels and bit width are inside the
+                                # compressed body: resolved at first decode
+                                ch.pages.append(
+                                    _Page(nvals, enc, None, 0, None, 0, False,
+                                          comp_off=ch.start + dpos,
+                                          comp_len=csz, ulen=usz))
+                                pos = dpos + csz
+                                continue
                             if max_def > 0:
-                                if dph.get(tc.DPH_DEF_ENCODING, RLE) != RLE:
-                                    raise Unsupported(f"{sc.name}: def-level encoding")
                                 dl = int.from_bytes(raw[body:body + 4], "little")
                                 def_off = ch.start + body + 4
                                 def_len = dl
@@ -178,14 +242,16 @@ class FileIndex:
                             raise Unsupported(f"{sc.name}: page type {ptype}")
                         pos = dpos + csz
                 out.append(ch)
-        self._chunks[ci] = out
+        self._chunks[(ci, snappy)] = out
+        if not any(ch.compressed for ch in out):
+            self._chunks[(ci, not snappy)] = out  # the switch changed nothing
         return out
 
 
 _INDEX_CACHE: Dict[Tuple[str, float, int], FileIndex] = {}
-#: merged device dictionaries per (file index id, column) — dictionary
-#: pages are file metadata-scale (MBs vs the GBs of codes re-decoded per
-#: scan); cached like the page index
+#: merged device dictionaries per (file index id, column, row-group window)
+#: — dictionary pages are file metadata-scale (MBs vs the GBs of codes
+#: re-decoded per scan); cached like the page index
 _DICT_CACHE: Dict[tuple, tuple] = {}
 
 
@@ -414,16 +480,21 @@ class _ColumnDecoder:
     restricts to row groups [lo, hi) — the out-of-core scan streams
     batches of row groups instead of whole files."""
 
-    def __init__(self, idx: FileIndex, name: str, device, rg_window=None):
+    def __init__(self, idx: FileIndex, name: str, device, rg_window=None,
+                 snappy: Optional[bool] = None):
         self.idx = idx
         self.device = device
         self.ci = idx.column_index(name)
         self.sc = idx.schema.column(self.ci)
         self.physical = self.sc.physical_type
         self.flba_w = self.sc.length or 0
-        self.chunks = idx.chunks(self.ci)
+        self.chunks = idx.chunks(self.ci, snappy)
         if rg_window is not None:
             self.chunks = self.chunks[rg_window[0]:rg_window[1]]
+        # merged dictionaries belong to the row groups they were built from:
+        # a window must not pick up another window's (or the whole file's)
+        self._dict_key = (id(idx), self.ci,
+                          None if rg_window is None else tuple(rg_window))
         self.pages = [p for ch in self.chunks for p in ch.pages]
         self.nrows = sum(p.nvals for p in self.pages)
         encs = {p.enc for p in self.pages}
@@ -444,9 +515,108 @@ class _ColumnDecoder:
         # absolute file offset -> offset within self.buf
         self.rel = {id(ch): offs[i] - ch.start
                     for i, ch in enumerate(self.chunks)}
+        if any(ch.compressed for ch in self.chunks):
+            self._decompress()
 
     def _off(self, ch: _Chunk, abs_off: int) -> int:
         return abs_off + self.rel[id(ch)]
+
+    # offsets of a page's regions within self.buf. Uncompressed: the file
+    # offset moved into the upload. Compressed: the page's base in the
+    # packed buffer plus the region's offset within the page.
+    def _def_off(self, ch: _Chunk, p: _Page) -> int:
+        if ch.compressed:
+            return self.pbase[id(p)] + p.def_off
+        return self._off(ch, p.def_off)
+
+    def _val_off(self, ch: _Chunk, p: _Page) -> int:
+        if ch.compressed:
+            return self.pbase[id(p)] + p.val_off
+        return self._off(ch, p.val_off)
+
+    def _dict_region(self, ch: _Chunk) -> Tuple[int, int]:
+        if ch.compressed:
+            return self.dbase[id(ch)], ch.dict_ulen
+        return self._off(ch, ch.dict_off), ch.dict_len
+
+    def _decompress(self):
+        """SNAPPY chunks: expand every page of the window (dictionary
+        pages too) with one launch into a packed buffer, make that buffer
+        self.buf, and resolve the page-internal layout of pages seen for
+        the first time."""
+        if not all(ch.compressed for ch in self.chunks):
+            raise Unsupported(f"{self.sc.name}: compressed and uncompressed "
+                              "row groups in one column")
+        rows = []
+        at = 0
+        self.pbase: Dict[int, int] = {}
+        self.dbase: Dict[int, int] = {}
+        for ch in self.chunks:
+            if ch.dict_off is not None:
+                rows.append((self._off(ch, ch.dict_off), ch.dict_len,
+                             ch.dict_ulen, at, 0, 0))
+                self.dbase[id(ch)] = at
+                at += ch.dict_ulen
+            for p in ch.pages:
+                rows.append((self._off(ch, p.comp_off), p.comp_len, p.ulen,
+                             at, 0, 0))
+                self.pbase[id(p)] = at
+                at += p.ulen
+        # +16 zeroed tail: the buffer contract of the page decoders
+        packed = torch.empty(at + 16, dtype=torch.uint8, device=self.device)
+        packed[at:] = 0
+        status = _ext().pq_snappy_decompress(
+            self.buf, _page_table(rows, self.device), packed)
+        bad = torch.nonzero(status).flatten()
+        if bad.numel():
+            i = int(bad[0].item())
+            raise Unsupported(f"{self.sc.name}: snappy page {i} of "
+                              f"{len(rows)} rejected, status "
+                              f"{int(status[i].item())}")
+        # the compressed upload is released here; its record_stream() keeps
+        # the allocator from reusing it before the decompress has run
+        self.buf = packed
+        self._resolve_pages()
+
+    def _resolve_pages(self):
+        """Fill def_len/all_valid/val_off/val_len/bw0 of compressed pages
+        not seen before: one gather of each page's first 16 bytes, and for
+        dictionary-encoded pages behind definition levels one more of the
+        bit-width byte at 4 + def_len."""
+        todo = [p for p in self.pages if not p.resolved]
+        if not todo:
+            return
+        max_def = self.sc.max_definition_level
+        bases = torch.tensor([self.pbase[id(p)] for p in todo],
+                             dtype=torch.int64, device=self.device)
+        # the packed buffer's 16-byte tail keeps base + 15 inside it
+        idx = bases.unsqueeze(1) + torch.arange(16, device=self.device)
+        heads = self.buf[idx.reshape(-1)].reshape(-1, 16).cpu().numpy()
+        layout = []
+        for p, head in zip(todo, heads):
+            raw = head.tobytes()
+            if max_def > 0:
+                dl = int.from_bytes(raw[:4], "little")
+                if p.ulen < 4 or dl > p.ulen - 4:
+                    raise Unsupported(f"{self.sc.name}: def-level length "
+                                      f"{dl} outside its page")
+                av = _check_all_valid(raw, 4, dl, p.nvals)
+                layout.append((4, dl, av, 4 + dl))
+            else:
+                layout.append((0, 0, True, 0))
+        bw = [0] * len(todo)
+        want = [k for k, p in enumerate(todo) if p.enc == RLE_DICTIONARY
+                and layout[k][3] < p.ulen]
+        if want:
+            at = torch.tensor(
+                [self.pbase[id(todo[k])] + layout[k][3] for k in want],
+                dtype=torch.int64, device=self.device)
+            for k, b in zip(want, self.buf[at].cpu().tolist()):
+                bw[k] = int(b)
+        for p, (doff, dl, av, voff), b in zip(todo, layout, bw):
+            p.def_off, p.def_len, p.all_valid = doff, dl, av
+            p.val_off, p.val_len, p.bw0 = voff, p.ulen - voff, b
+            p.resolved = True
 
     # -- validity ---------------------------------------------------------
     def decode_validity(self):
@@ -460,7 +630,7 @@ class _ColumnDecoder:
                 if p.all_valid or p.def_len == 0:
                     rows.append((0, 0, 0, base, 0, 1))  # filled below
                 else:
-                    rows.append((self._off(ch, p.def_off), p.def_len,
+                    rows.append((self._def_off(ch, p), p.def_len,
                                  p.nvals, base, 0, 1))
                 base += p.nvals
         ext = _ext()
@@ -518,14 +688,14 @@ class _ColumnDecoder:
                 b = int(dense_base[pi])
                 c = dense_counts[pi]
                 if p.enc == PLAIN:
-                    plain_rows.append((self._off(ch, p.val_off), p.val_len,
+                    plain_rows.append((self._val_off(ch, p), p.val_len,
                                        c, b, 0, width))
                 elif p.enc == RLE_DICTIONARY:
-                    bw_off = self._off(ch, p.val_off)
+                    bw_off = self._val_off(ch, p)
                     dict_rows.append((bw_off, p.val_len, c, b, 0, p.bw0))
                     dict_chunks.append((ch, b, c))
                 elif p.enc == DELTA_BINARY_PACKED:
-                    delta_rows.append((self._off(ch, p.val_off), p.val_len,
+                    delta_rows.append((self._val_off(ch, p), p.val_len,
                                        c, b, 0, 0))
                     delta_counts.append(c)
                 pi += 1
@@ -622,8 +792,8 @@ class _ColumnDecoder:
         (offsets int64[n+1], bytes u8) tensors."""
         if ch.dict_off is None:
             raise Unsupported(f"{self.sc.name}: dict-encoded page, no dict")
-        rows = [(self._off(ch, ch.dict_off), ch.dict_len, ch.dict_nvals,
-                 0, 0, 0)]
+        d_off, d_len = self._dict_region(ch)
+        rows = [(d_off, d_len, ch.dict_nvals, 0, 0, 0)]
         table = _page_table(rows, self.device)
         lengths, src_pos = ext.pq_bytearray_walk(self.buf, table,
                                                  ch.dict_nvals)
@@ -651,9 +821,14 @@ class _ColumnDecoder:
             return cache[key]
         if ch.dict_off is None:
             raise Unsupported(f"{self.sc.name}: dict-encoded page, no dict")
-        with open(self.idx.path, "rb") as f:
-            f.seek(ch.dict_off)
-            raw = f.read(ch.dict_len)
+        if ch.compressed:
+            # the decompressed dictionary page is in the packed buffer
+            d_off, d_len = self._dict_region(ch)
+            raw = self.buf[d_off:d_off + d_len].cpu().numpy().tobytes()
+        else:
+            with open(self.idx.path, "rb") as f:
+                f.seek(ch.dict_off)
+                raw = f.read(ch.dict_len)
         vals = _decode_dict_host(raw, self.physical, ch.dict_nvals, self.flba_w)
         cache[key] = vals
         return vals
@@ -668,12 +843,12 @@ class _ColumnDecoder:
             pi = 0
             for ch in self.chunks:
                 for p in ch.pages:
-                    dict_rows.append((self._off(ch, p.val_off), p.val_len,
+                    dict_rows.append((self._val_off(ch, p), p.val_len,
                                       dense_counts[pi], int(dense_base[pi]),
                                       0, p.bw0))
                     pi += 1
             codes_dense = self._decode_dict_codes(ext, dict_rows)
-            cached = _DICT_CACHE.get((id(self.idx), self.ci))
+            cached = _DICT_CACHE.get(self._dict_key)
             if cached is not None:
                 # merged dictionary + per-chunk entry remaps are a pure
                 # function of the FILE (like the page index): cache them
@@ -696,7 +871,7 @@ class _ColumnDecoder:
                 o0, b0 = dict_cols[0]
                 d_offs, d_bytes, old_to_new = _lex_sort_dict(o0, b0)
                 entry_codes, entry_bases = old_to_new, [0]
-                _DICT_CACHE[(id(self.idx), self.ci)] = (
+                _DICT_CACHE[self._dict_key] = (
                     d_offs, d_bytes, entry_codes, entry_bases)
                 self._remap_codes(codes_dense, dense_counts, entry_codes,
                                   entry_bases)
@@ -727,7 +902,7 @@ class _ColumnDecoder:
                 for o, _b2 in dict_cols:
                     entry_bases.append(eb)
                     eb += o.numel() - 1
-                _DICT_CACHE[(id(self.idx), self.ci)] = (
+                _DICT_CACHE[self._dict_key] = (
                     d_offs, d_bytes, entry_codes, entry_bases)
                 self._remap_codes(codes_dense, dense_counts, entry_codes,
                                   entry_bases)
@@ -739,7 +914,7 @@ class _ColumnDecoder:
             pi = 0
             for ch in self.chunks:
                 for p in ch.pages:
-                    rows.append((self._off(ch, p.val_off), p.val_len,
+                    rows.append((self._val_off(ch, p), p.val_len,
                                  dense_counts[pi], int(dense_base[pi]), 0, 0))
                     pi += 1
             deltas, data_end = ext.pq_delta_decode(
@@ -778,7 +953,7 @@ class _ColumnDecoder:
         pi = 0
         for ch in self.chunks:
             for p in ch.pages:
-                rows.append((self._off(ch, p.val_off), p.val_len,
+                rows.append((self._val_off(ch, p), p.val_len,
                              dense_counts[pi], int(dense_base[pi]), 0, 0))
                 pi += 1
         lengths, src_pos = ext.pq_bytearray_walk(
@@ -848,9 +1023,12 @@ class _ColumnDecoder:
         raise Unsupported(f"{self.sc.name}: arrow type {at}")
 
 
-def read_gpu(files: List[str], schema, device, rg_window=None) -> Table:
+def read_gpu(files: List[str], schema, device, rg_window=None,
+             snappy: Optional[bool] = None) -> Table:
     """Decode `schema`'s columns of the given parquet files on the GPU.
-    Raises Unsupported when any file/column needs the host fallback."""
+    Raises Unsupported when any file/column needs the host fallback.
+    `snappy` turns device Snappy decompression on or off (None: the
+    SAIL_IO_GPU_SNAPPY environment switch, default off)."""
     if not str(device).startswith("cuda") and not _ALLOW_CPU:
         raise Unsupported("gpu decode needs a cuda device")
     from ..engine.executor import concat_columns
@@ -862,7 +1040,8 @@ def read_gpu(files: List[str], schema, device, rg_window=None) -> Table:
         names = [n for n, _ in schema] if schema else [
             idx.schema.column(i).name for i in range(len(idx.schema))]
         for n in names:
-            dec = _ColumnDecoder(idx, n, device, rg_window=rg_window)
+            dec = _ColumnDecoder(idx, n, device, rg_window=rg_window,
+                                 snappy=snappy)
             col, _ = dec.decode()
             cols[n] = col
         per_file.append(cols)

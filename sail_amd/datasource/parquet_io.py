@@ -112,7 +112,9 @@ def _try_read_gpu(files: List[str], schema, device, options):
     from . import gpu_parquet
 
     try:
-        return gpu_parquet.read_gpu(files, schema, device)
+        return gpu_parquet.read_gpu(
+            files, schema, device,
+            snappy=gpu_parquet.snappy_enabled(options))
     except gpu_parquet.Unsupported:
         if mode == "force":
             raise
@@ -238,8 +240,9 @@ def scan_batches(paths: List[str], schema, device, options: Dict[str, str],
             hi = min(lo + step, nrg)
             if use_gpu:
                 try:
-                    yield gpu_parquet.read_gpu([f], schema, device,
-                                               rg_window=(lo, hi))
+                    yield gpu_parquet.read_gpu(
+                        [f], schema, device, rg_window=(lo, hi),
+                        snappy=gpu_parquet.snappy_enabled(options))
                     continue
                 except gpu_parquet.Unsupported:
                     if mode == "force":

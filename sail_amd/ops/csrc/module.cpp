@@ -37,6 +37,9 @@ std::vector<torch::Tensor> pq_delta_decode(torch::Tensor buf, torch::Tensor page
 std::vector<torch::Tensor> pq_bytearray_walk(torch::Tensor buf, torch::Tensor pages,
                                              int64_t total);
 void pq_segscan(torch::Tensor data, torch::Tensor pages);
+// snappy.hip
+torch::Tensor pq_snappy_decompress(torch::Tensor buf, torch::Tensor pages,
+                                   torch::Tensor out);
 // mfma_reduce.hip
 torch::Tensor mfma_sum_f64(torch::Tensor x, bool use_mfma);
 torch::Tensor pq_gather_strings(torch::Tensor buf, torch::Tensor src_pos,
@@ -70,4 +73,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_sum_f64", &mfma_sum_f64,
         "f64 sum via v_mfma_f64_16x16x4 (measurement harness vs VALU)");
   m.def("pq_gather_strings", &pq_gather_strings, "gather byte_array payloads");
+  // snappy.hip has its own case table (tests/test_snappy_kernel.py), apart
+  // from the page-decoder table that tests/test_pq_kernels.py keeps complete
+  m.def(
+      "pq_snappy_decompress", &pq_snappy_decompress,
+      "parquet Snappy page decompression -> per-page status");
 }

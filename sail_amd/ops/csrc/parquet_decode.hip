@@ -14,7 +14,8 @@
 // Encodings: PLAIN (fixed width + byte_array), RLE/bit-packed hybrid
 // (definition levels, RLE_DICTIONARY indices), DELTA_BINARY_PACKED,
 // DELTA_LENGTH_BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY decimals.
-// Compressed pages and v2 data pages take the host fallback
+// SNAPPY pages are expanded first by snappy.hip when sail.io.gpu_snappy is
+// on; other codecs and v2 data pages take the host fallback
 // (datasource/parquet_io.py).
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>

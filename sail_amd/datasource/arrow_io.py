@@ -165,7 +165,9 @@ def arrow_column(col: pa.ChunkedArray, device="cpu", dict_encode=True) -> Column
             if pa.types.is_date32(at):
                 data = torch.frombuffer(arr.buffers()[1], dtype=torch.int32)[: len(arr)].clone().to(device)
             elif at.equals(pa.bool_()):
-                np_data = arr.to_numpy(zero_copy_only=False)
+                # with nulls to_numpy would hand back objects; the null
+                # slots are masked by the validity below
+                np_data = arr.fill_null(False).to_numpy(zero_copy_only=False)
                 data = torch.from_numpy(np.ascontiguousarray(np_data)).to(tt).to(device)
             else:
                 data = torch.frombuffer(arr.buffers()[1], dtype=tt)[: len(arr)].clone().to(device)

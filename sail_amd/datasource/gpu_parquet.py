@@ -5,14 +5,25 @@ The reference scans parquet with arrow-rs on the CPU
 crates/sail-common/src/config/application.yaml:424-521). Here the decode
 itself runs on the MI355X: the host reads raw column-chunk bytes (pinned
 staging -> HBM), parses page headers once per file (utils/thrift_compact),
-and launches batched page-table kernels (ops/csrc/parquet_decode.hip).
+and launches batched page-table kernels (ops/csrc/parquet_decode.hip,
+ops/csrc/parquet_types.hip).
 Decoded columns are born as device tensors — no pyarrow on the hot path.
 
-Supported: uncompressed v1 data pages, PLAIN fixed-width, PLAIN
-byte_array, RLE_DICTIONARY (+PLAIN dictionary pages), DELTA_BINARY_PACKED,
-DELTA_LENGTH_BYTE_ARRAY, FLBA/INT32/INT64 decimals, definition levels
-(nulls). Anything else raises Unsupported and the caller falls back to the
-host pyarrow path (parquet_io.read).
+Supported: uncompressed v1 and v2 data pages (mixed freely within a
+column), PLAIN fixed-width, PLAIN byte_array, RLE_DICTIONARY (+PLAIN
+dictionary pages), DELTA_BINARY_PACKED, DELTA_LENGTH_BYTE_ARRAY,
+BYTE_STREAM_SPLIT on INT32/INT64/FLOAT/DOUBLE, BOOLEAN (PLAIN and RLE),
+INT96 timestamps (PLAIN and dictionary; decoded to int64 microseconds),
+FLBA/INT32/INT64 decimals, definition levels (nulls). Anything else raises
+Unsupported and the caller falls back to the host pyarrow path
+(parquet_io.read): v2 pages in a compressed chunk, codecs other than
+opt-in Snappy, DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT on FIXED_LEN_BYTE_ARRAY,
+dictionary-encoded BOOLEAN, nested columns.
+
+A v2 page keeps its levels outside the value region and says in its header
+how long they are and how many values are null, so its layout and dense
+(non-null) count are known at index time: no length prefix to read, and no
+per-page count to fetch from the device.
 
 Opt-in (config sail.io.gpu_snappy / env SAIL_IO_GPU_SNAPPY / read option
 gpuSnappy, default off): SNAPPY column chunks with v1 data pages. The
@@ -24,7 +35,8 @@ definition levels and the dictionary bit-width byte are inside the
 compressed body, so they are resolved after the first decompress of a
 column from two small device->host gathers and cached on the page index.
 A page the kernel rejects (non-zero status) raises Unsupported. Other
-codecs, v2 data pages and pages of 2^31 bytes or more stay on the host path.
+codecs, v2 data pages in a compressed chunk and pages of 2^31 bytes or
+more stay on the host path.
 """
 from __future__ import annotations
 
@@ -45,7 +57,10 @@ RLE = 3
 DELTA_BINARY_PACKED = 5
 DELTA_LENGTH_BYTE_ARRAY = 6
 RLE_DICTIONARY = 8
+BYTE_STREAM_SPLIT = 9
 
+_JULIAN_UNIX_EPOCH = 2440588          # Julian day number of 1970-01-01
+_MICROS_PER_DAY = 86_400_000_000
 
 _MAX_PAGE = 1 << 31   # pq_snappy_decompress takes lengths below 2^31
 
@@ -71,15 +86,19 @@ class _Page:
     compressed body in the file, ulen its uncompressed length, and
     def_off/val_off are relative to the start of the decompressed body;
     they, def_len, val_len, all_valid and bw0 are filled in on the first
-    decode (`resolved`)."""
+    decode (`resolved`). `ndense` is the non-null count where the page
+    header states it (v2 pages: num_values - num_nulls), else None and the
+    count comes from the decoded definition levels."""
 
     __slots__ = ("nvals", "enc", "def_off", "def_len", "val_off", "val_len",
                  "all_valid", "bw0", "comp_off", "comp_len", "ulen",
-                 "resolved")
+                 "resolved", "ndense")
 
     def __init__(self, nvals, enc, def_off, def_len, val_off, val_len,
-                 all_valid, bw0=0, comp_off=None, comp_len=0, ulen=0):
+                 all_valid, bw0=0, comp_off=None, comp_len=0, ulen=0,
+                 ndense=None):
         self.nvals = nvals
+        self.ndense = ndense
         self.enc = enc
         self.def_off = def_off    # absolute file offset of RLE def runs
         self.def_len = def_len
@@ -154,6 +173,36 @@ class FileIndex:
         if name not in self._cols:
             raise Unsupported(f"column {name} not in {self.path}")
         return self._cols[name]
+
+    @staticmethod
+    def _v2_page(name, dph, raw, start, dpos, csz, max_def) -> _Page:
+        """Index one uncompressed DATA_PAGE_V2 whose body is raw[dpos:
+        dpos + csz]: repetition levels, definition levels (bare RLE-hybrid
+        runs, no length prefix), values; lengths and null count are in the
+        header."""
+        nvals = dph.get(tc.DPH2_NUM_VALUES, 0)
+        nnull = dph.get(tc.DPH2_NUM_NULLS, 0)
+        enc = dph.get(tc.DPH2_ENCODING, PLAIN)
+        if enc == PLAIN_DICTIONARY:
+            enc = RLE_DICTIONARY
+        dl = dph.get(tc.DPH2_DEF_LEVELS_BYTE_LENGTH, 0)
+        rl = dph.get(tc.DPH2_REP_LEVELS_BYTE_LENGTH, 0)
+        if rl != 0:
+            raise Unsupported(f"{name}: repetition levels in a v2 page")
+        if not (0 <= nnull <= nvals and 0 <= dl <= csz):
+            raise Unsupported(f"{name}: v2 page header out of range")
+        if nnull and (max_def == 0 or dl == 0):
+            raise Unsupported(f"{name}: v2 page with nulls but no "
+                              "definition levels")
+        body = dpos + dl
+        val_len = csz - dl
+        bw0 = raw[body] if enc == RLE_DICTIONARY and val_len > 0 else 0
+        if max_def > 0:
+            def_off, def_len = start + dpos, dl
+        else:
+            def_off, def_len = 0, 0
+        return _Page(nvals, enc, def_off, def_len, start + body, val_len,
+                     nnull == 0, bw0, ndense=nvals - nnull)
 
     def chunks(self, ci: int, snappy: Optional[bool] = None) -> List[_Chunk]:
         """Page tables of column `ci`. `snappy` accepts SNAPPY chunks
@@ -238,6 +287,10 @@ class FileIndex:
                             ch.pages.append(
                                 _Page(nvals, enc, def_off, def_len, val_off,
                                       val_len, av, bw0))
+                        elif ptype == 3 and not comp:  # data page v2
+                            ch.pages.append(self._v2_page(
+                                sc.name, hdr.get(tc.DATA_PAGE_HEADER_V2, {}),
+                                raw, ch.start, dpos, csz, max_def))
                         else:
                             raise Unsupported(f"{sc.name}: page type {ptype}")
                         pos = dpos + csz
@@ -459,6 +512,19 @@ def _decode_dict_host(raw: bytes, physical: str, nvals: int, flba_w: int):
         return np.frombuffer(raw, dtype="<f8", count=nvals).copy()
     if physical == "FLOAT":
         return np.frombuffer(raw, dtype="<f4", count=nvals).copy()
+    if physical == "INT96":
+        # same arithmetic as pq_int96_micros: truncating division (fmod
+        # keeps the dividend's sign), wrapping int64
+        if len(raw) < 12 * nvals:
+            raise Unsupported("INT96 dict page shorter than its values")
+        b = np.frombuffer(raw, dtype=np.uint8,
+                          count=nvals * 12).reshape(nvals, 12)
+        nanos = np.ascontiguousarray(b[:, :8]).view("<i8").reshape(nvals)
+        days = np.ascontiguousarray(b[:, 8:]).view("<i4").reshape(nvals) \
+            .astype(np.int64) - _JULIAN_UNIX_EPOCH
+        with np.errstate(over="ignore"):
+            return days * np.int64(_MICROS_PER_DAY) + \
+                (nanos - np.fmod(nanos, 1000)) // 1000
     if physical == "FIXED_LEN_BYTE_ARRAY":
         b = np.frombuffer(raw, dtype=np.uint8,
                           count=nvals * flba_w).reshape(nvals, flba_w)
@@ -498,14 +564,23 @@ class _ColumnDecoder:
         self.pages = [p for ch in self.chunks for p in ch.pages]
         self.nrows = sum(p.nvals for p in self.pages)
         encs = {p.enc for p in self.pages}
-        bad = encs - {PLAIN, RLE_DICTIONARY, DELTA_BINARY_PACKED,
-                      DELTA_LENGTH_BYTE_ARRAY}
+        if self.physical == "BOOLEAN":
+            ok = {PLAIN, RLE}
+        elif self.physical == "INT96":
+            ok = {PLAIN, RLE_DICTIONARY}
+        else:
+            ok = {PLAIN, RLE_DICTIONARY, DELTA_BINARY_PACKED,
+                  DELTA_LENGTH_BYTE_ARRAY}
+            if self.physical in _PHYS_WIDTH:
+                ok.add(BYTE_STREAM_SPLIT)
+        bad = encs - ok
         if bad:
             raise Unsupported(f"{self.sc.name}: encodings {bad}")
         if self.physical == "BYTE_ARRAY" and len(encs) > 1:
             raise Unsupported(f"{self.sc.name}: mixed string encodings {encs}")
         if self.physical not in ("INT32", "INT64", "FLOAT", "DOUBLE",
-                                 "BYTE_ARRAY", "FIXED_LEN_BYTE_ARRAY"):
+                                 "BYTE_ARRAY", "FIXED_LEN_BYTE_ARRAY",
+                                 "BOOLEAN", "INT96"):
             raise Unsupported(f"{self.sc.name}: physical {self.physical}")
 
     # -- staging ----------------------------------------------------------
@@ -646,8 +721,12 @@ class _ColumnDecoder:
         counts = []
         base = 0
         for p in self.pages:
-            counts.append(int(valid[base:base + p.nvals].sum().item())
-                          if not p.all_valid else p.nvals)
+            if p.all_valid:
+                counts.append(p.nvals)
+            elif p.ndense is not None:
+                counts.append(p.ndense)   # v2 header: no device round trip
+            else:
+                counts.append(int(valid[base:base + p.nvals].sum().item()))
             base += p.nvals
         return valid.to(torch.uint8), counts
 
@@ -666,28 +745,44 @@ class _ColumnDecoder:
             col = self._decode_strings(ext, validity, dense_counts, dense_base)
             return col, validity
 
-        # fixed-width physical types (possibly mixed PLAIN/dict/delta pages)
-        width = self.flba_w if self.physical == "FIXED_LEN_BYTE_ARRAY" \
-            else _PHYS_WIDTH[self.physical]
+        # fixed-width physical types; the pages of a column may mix the
+        # row classes plain, dict, delta, byte-stream-split and RLE booleans
+        if self.physical == "FIXED_LEN_BYTE_ARRAY":
+            width, dt = self.flba_w, torch.int64
+        elif self.physical == "BOOLEAN":
+            width, dt = 0, torch.uint8      # bit-packed; one byte per value
+        elif self.physical == "INT96":
+            width, dt = 12, torch.int64     # decoded to epoch microseconds
+        else:
+            width = _PHYS_WIDTH[self.physical]
+            dt = _PHYS_TORCH[self.physical]
         dense: Optional[torch.Tensor] = None
 
         def _out():
             nonlocal dense
             if dense is None:
-                dt = (torch.int64 if self.physical == "FIXED_LEN_BYTE_ARRAY"
-                      else _PHYS_TORCH[self.physical])
                 dense = torch.empty(n_dense, dtype=dt, device=dev)
             return dense
 
-        plain_rows, dict_rows, delta_rows = [], [], []
-        delta_counts = []
+        plain_rows, dict_rows, delta_rows, bss_rows, rle_rows = \
+            [], [], [], [], []
         dict_chunks = []  # (chunk, page row ranges) needing dict values
         pi = 0
+
+        def _short(what):
+            return Unsupported(f"{self.sc.name}: page {pi}: {what}")
+
+        # the value kernels trust n_values: every region is checked against
+        # it here, while the table is still on the host
         for ch in self.chunks:
             for p in ch.pages:
                 b = int(dense_base[pi])
                 c = dense_counts[pi]
                 if p.enc == PLAIN:
+                    if self.physical == "BOOLEAN" and p.val_len * 8 < c:
+                        raise _short(f"{p.val_len} bytes for {c} booleans")
+                    if self.physical == "INT96" and p.val_len < 12 * c:
+                        raise _short(f"{p.val_len} bytes for {c} INT96 values")
                     plain_rows.append((self._val_off(ch, p), p.val_len,
                                        c, b, 0, width))
                 elif p.enc == RLE_DICTIONARY:
@@ -697,31 +792,62 @@ class _ColumnDecoder:
                 elif p.enc == DELTA_BINARY_PACKED:
                     delta_rows.append((self._val_off(ch, p), p.val_len,
                                        c, b, 0, 0))
-                    delta_counts.append(c)
+                elif p.enc == BYTE_STREAM_SPLIT:
+                    if p.val_len != width * c:
+                        raise _short(f"{p.val_len} bytes for {c} "
+                                     f"byte-stream-split values of {width}")
+                    bss_rows.append((self._val_off(ch, p), p.val_len,
+                                     c, b, 0, 0))
+                elif p.enc == RLE:
+                    # RLE booleans: 4-byte length prefix, then hybrid runs
+                    # of width 1. A page of nulls only has no value bytes.
+                    if c == 0:
+                        rle_rows.append((0, 0, 0, b, 0, 1))
+                    elif p.val_len < 4:
+                        raise _short(f"{p.val_len} bytes for {c} RLE booleans")
+                    else:
+                        rle_rows.append((self._val_off(ch, p) + 4,
+                                         p.val_len - 4, c, b, 0, 1))
                 pi += 1
+
+        def _place(rows, vals):
+            """Rows of one class decoded into `vals` (n_dense long, written
+            at each page's out_row): the column itself when every page is of
+            that class, else copied page by page into the common output."""
+            nonlocal dense
+            if len(rows) == pi:
+                dense = vals if vals.dtype == dt else vals.to(dt)
+            else:
+                o = _out()
+                for r in rows:
+                    o[r[3]:r[3] + r[2]] = vals[r[3]:r[3] + r[2]]
 
         if plain_rows:
             # kernels write at out_row (dense row base); the output tensor
             # covers all n_dense rows even when other pages use another enc
+            table = _page_table(plain_rows, dev)
             if self.physical == "FIXED_LEN_BYTE_ARRAY":
-                flba = ext.pq_flba_i64(self.buf, _page_table(plain_rows, dev),
-                                       n_dense, width)
-                if len(plain_rows) == pi:
-                    dense = flba
-                else:
-                    o = _out()
-                    for r in plain_rows:
-                        o[r[3]:r[3] + r[2]] = flba[r[3]:r[3] + r[2]]
+                _place(plain_rows,
+                       ext.pq_flba_i64(self.buf, table, n_dense, width))
+            elif self.physical == "BOOLEAN":
+                _place(plain_rows,
+                       ext.pq_bool_unpack(self.buf, table, n_dense))
+            elif self.physical == "INT96":
+                _place(plain_rows,
+                       ext.pq_int96_micros(self.buf, table, n_dense))
             else:
-                raw = ext.pq_plain_copy(self.buf, _page_table(plain_rows, dev),
-                                        n_dense, width)
-                typed = raw.view(_PHYS_TORCH[self.physical])
-                if len(plain_rows) == pi:
-                    dense = typed
-                else:
-                    o = _out()
-                    for r in plain_rows:
-                        o[r[3]:r[3] + r[2]] = typed[r[3]:r[3] + r[2]]
+                raw = ext.pq_plain_copy(self.buf, table, n_dense, width)
+                _place(plain_rows, raw.view(dt))
+
+        if bss_rows:
+            raw = ext.pq_bss_decode(self.buf, _page_table(bss_rows, dev),
+                                    n_dense, width)
+            _place(bss_rows, raw.view(dt))
+
+        if rle_rows:
+            bits = ext.pq_rle_decode(self.buf, _page_table(rle_rows, dev),
+                                     n_dense)
+            _place(rle_rows, bits)
 
         if delta_rows:
             if self.physical not in ("INT32", "INT64"):
@@ -733,13 +859,7 @@ class _ColumnDecoder:
             # finish [first, d1, ...] -> values with the on-device per-page
             # scan (replaces torch.cumsum + cat + correction gathers)
             ext.pq_segscan(deltas, table)
-            if len(delta_rows) == pi:
-                dense = deltas.to(_PHYS_TORCH[self.physical]) \
-                    if self.physical == "INT32" else deltas
-            else:
-                o = _out()
-                for r, c in zip(delta_rows, delta_counts):
-                    o[r[3]:r[3] + c] = deltas[r[3]:r[3] + c].to(o.dtype)
+            _place(delta_rows, deltas)
 
         if dict_rows:
             codes = self._decode_dict_codes(ext, dict_rows)
@@ -1003,6 +1123,14 @@ class _ColumnDecoder:
             return Column(dt, full.to(torch.int64), validity)
         if pa.types.is_date32(at):
             return Column(T.DATE, full.to(torch.int32), validity)
+        if self.physical == "BOOLEAN":
+            if not pa.types.is_boolean(at):
+                raise Unsupported(f"{self.sc.name}: arrow type {at}")
+            return Column(T.BOOL, full.to(torch.bool), validity)
+        if self.physical == "INT96":
+            # the file's arrow type says timestamp[ns]; the INT96 decoders
+            # already produced the engine's epoch microseconds
+            return Column(T.TIMESTAMP, full, validity)
         if pa.types.is_timestamp(at):
             unit = at.unit
             v = full.to(torch.int64)

@@ -40,6 +40,11 @@ void pq_segscan(torch::Tensor data, torch::Tensor pages);
 // snappy.hip
 torch::Tensor pq_snappy_decompress(torch::Tensor buf, torch::Tensor pages,
                                    torch::Tensor out);
+// parquet_types.hip
+torch::Tensor pq_bool_unpack(torch::Tensor buf, torch::Tensor pages, int64_t total);
+torch::Tensor pq_int96_micros(torch::Tensor buf, torch::Tensor pages, int64_t total);
+torch::Tensor pq_bss_decode(torch::Tensor buf, torch::Tensor pages, int64_t total,
+                            int64_t width);
 // mfma_reduce.hip
 torch::Tensor mfma_sum_f64(torch::Tensor x, bool use_mfma);
 torch::Tensor pq_gather_strings(torch::Tensor buf, torch::Tensor src_pos,
@@ -78,4 +83,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def(
       "pq_snappy_decompress", &pq_snappy_decompress,
       "parquet Snappy page decompression -> per-page status");
+  // parquet_types.hip: case table in tests/test_pq_types_kernels.py
+  m.def(
+      "pq_bool_unpack", &pq_bool_unpack,
+      "parquet PLAIN BOOLEAN bit unpack -> uint8 0/1");
+  m.def(
+      "pq_int96_micros", &pq_int96_micros,
+      "parquet PLAIN INT96 timestamp -> int64 microseconds since the epoch");
+  m.def(
+      "pq_bss_decode", &pq_bss_decode,
+      "parquet BYTE_STREAM_SPLIT decode, width 4 or 8");
 }

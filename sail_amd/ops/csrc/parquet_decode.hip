@@ -13,10 +13,15 @@
 //
 // Encodings: PLAIN (fixed width + byte_array), RLE/bit-packed hybrid
 // (definition levels, RLE_DICTIONARY indices), DELTA_BINARY_PACKED,
-// DELTA_LENGTH_BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY decimals.
-// SNAPPY pages are expanded first by snappy.hip when sail.io.gpu_snappy is
-// on; other codecs and v2 data pages take the host fallback
-// (datasource/parquet_io.py).
+// DELTA_LENGTH_BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY decimals. PLAIN BOOLEAN,
+// PLAIN INT96 and BYTE_STREAM_SPLIT are in parquet_types.hip; RLE booleans
+// are hybrid runs of width 1 and use rle_decode_kernel.
+// The kernels see value and level regions only, so v1 and v2 data pages
+// look the same to them (the host finds the regions). SNAPPY v1 pages are
+// expanded first by snappy.hip when sail.io.gpu_snappy is on. Still on the
+// host fallback (datasource/parquet_io.py): v2 pages in a compressed chunk,
+// other codecs, DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT on FIXED_LEN_BYTE_ARRAY,
+// nested columns.
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>

@@ -263,6 +263,14 @@ DPH_NUM_VALUES = 1
 DPH_ENCODING = 2
 DPH_DEF_ENCODING = 3
 DPH_REP_ENCODING = 4
+# DataPageHeaderV2
+DPH2_NUM_VALUES = 1
+DPH2_NUM_NULLS = 2
+DPH2_NUM_ROWS = 3
+DPH2_ENCODING = 4
+DPH2_DEF_LEVELS_BYTE_LENGTH = 5
+DPH2_REP_LEVELS_BYTE_LENGTH = 6
+DPH2_IS_COMPRESSED = 7   # absent means true
 # DictionaryPageHeader
 DICT_NUM_VALUES = 1
 DICT_ENCODING = 2

@@ -25,6 +25,14 @@ how long they are and how many values are null, so its layout and dense
 (non-null) count are known at index time: no length prefix to read, and no
 per-page count to fetch from the device.
 
+DELTA_BINARY_PACKED integer pages decode with one launch of pq_delta_values
+(ops/csrc/parquet_delta.hip), which writes final values of the column's own
+width; SAIL_IO_GPU_DELTA_FUSED=off selects the older pq_delta_decode +
+pq_segscan + cast. The finished page tables of a fixed-width column depend
+only on the file, the column and the row-group window, so they are built
+once, kept on the FileIndex with their device copies (_Tables, at most
+TABLE_CACHE_CAP bytes per process) and reused by every later scan.
+
 Opt-in (config sail.io.gpu_snappy / env SAIL_IO_GPU_SNAPPY / read option
 gpuSnappy, default off): SNAPPY column chunks with v1 data pages. The
 compressed chunk bytes are uploaded as they are, one launch of
@@ -40,6 +48,7 @@ more stay on the host path.
 """
 from __future__ import annotations
 
+import collections
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -78,6 +87,66 @@ def snappy_enabled(options=None) -> bool:
     else:
         v = os.environ.get("SAIL_IO_GPU_SNAPPY", "off")
     return str(v).lower() in ("on", "true", "1")
+
+
+def delta_fused_enabled() -> bool:
+    """SAIL_IO_GPU_DELTA_FUSED (config sail.io.gpu_delta_fused), default on:
+    DELTA_BINARY_PACKED integer pages decode with one pq_delta_values launch.
+    `off`, `0` or `false` selects pq_delta_decode + pq_segscan + cast. Read
+    on every decode, so one process can alternate the two paths."""
+    v = os.environ.get("SAIL_IO_GPU_DELTA_FUSED", "on")
+    return str(v).lower() not in ("off", "false", "0")
+
+
+#: Cap on the bytes of cached page tables (host array plus device copy) held
+#: by one process; least recently used entries go first. A 600M-row column
+#: of 30,000 pages is 1.4 MB on each side.
+TABLE_CACHE_CAP = 256 << 20
+_TABLE_LRU: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict()
+_table_bytes = 0
+
+
+class _Tables:
+    """The finished page tables of one fixed-width column window: per row
+    class the int64 [n,6] array and its device copy, and what decode() needs
+    beside them. A pure function of file, column, row-group window and
+    Snappy switch while every chunk is uncompressed: the upload-relative
+    offsets are cumulative chunk lengths."""
+
+    __slots__ = ("n_pages", "n_dense", "all_valid", "rows", "dev",
+                 "delta_total", "dict_chunks", "nbytes")
+
+    def __init__(self, n_pages, n_dense, all_valid, classes, dict_chunks,
+                 device):
+        self.n_pages = n_pages
+        self.n_dense = n_dense
+        self.all_valid = all_valid
+        self.rows: Dict[str, np.ndarray] = {}
+        self.dev: Dict[str, torch.Tensor] = {}
+        for name, rows in classes.items():
+            arr = np.asarray(rows, dtype=np.int64).reshape(-1, 6)
+            self.rows[name] = arr
+            if len(arr):
+                self.dev[name] = torch.from_numpy(arr).to(device)
+        d = self.rows["delta"]
+        self.delta_total = int((d[:, 3] + d[:, 2]).max()) if len(d) else 0
+        self.dict_chunks = dict_chunks
+        self.nbytes = 2 * sum(a.nbytes for a in self.rows.values())
+
+
+def _remember_tables(idx: "FileIndex", key, entry: _Tables):
+    """Keep `entry` on its FileIndex, dropping the least recently used
+    entries of the process while over TABLE_CACHE_CAP."""
+    global _table_bytes
+    if entry.nbytes > TABLE_CACHE_CAP:
+        return
+    idx._tables[key] = entry
+    _TABLE_LRU[(id(idx), key)] = (idx, entry.nbytes)
+    _table_bytes += entry.nbytes
+    while _table_bytes > TABLE_CACHE_CAP:
+        (_, old_key), (old_idx, n) = _TABLE_LRU.popitem(last=False)
+        old_idx._tables.pop(old_key, None)
+        _table_bytes -= n
 
 
 class _Page:
@@ -168,6 +237,10 @@ class FileIndex:
         # keyed by (column, snappy switch): an index built with the switch
         # off must not answer for one built with it on
         self._chunks: Dict[Tuple[int, bool], List[_Chunk]] = {}
+        # per (column, row-group window, snappy switch): the flat page list
+        # with its totals, and the finished page tables (_Tables)
+        self._windows: Dict[tuple, tuple] = {}
+        self._tables: Dict[tuple, _Tables] = {}
 
     def column_index(self, name: str) -> int:
         if name not in self._cols:
@@ -554,16 +627,23 @@ class _ColumnDecoder:
         self.sc = idx.schema.column(self.ci)
         self.physical = self.sc.physical_type
         self.flba_w = self.sc.length or 0
+        snappy = snappy_enabled() if snappy is None else bool(snappy)
         self.chunks = idx.chunks(self.ci, snappy)
+        window = None if rg_window is None else tuple(rg_window)
         if rg_window is not None:
             self.chunks = self.chunks[rg_window[0]:rg_window[1]]
         # merged dictionaries belong to the row groups they were built from:
         # a window must not pick up another window's (or the whole file's)
-        self._dict_key = (id(idx), self.ci,
-                          None if rg_window is None else tuple(rg_window))
-        self.pages = [p for ch in self.chunks for p in ch.pages]
-        self.nrows = sum(p.nvals for p in self.pages)
-        encs = {p.enc for p in self.pages}
+        self._dict_key = (id(idx), self.ci, window)
+        # the page list of a window never changes: flattened once per index
+        self._win_key = (self.ci, window, snappy, str(device))
+        meta = idx._windows.get(self._win_key)
+        if meta is None:
+            pages = [p for ch in self.chunks for p in ch.pages]
+            meta = (pages, sum(p.nvals for p in pages), {p.enc for p in pages},
+                    any(ch.compressed for ch in self.chunks))
+            idx._windows[self._win_key] = meta
+        self.pages, self.nrows, encs, self.compressed = meta
         if self.physical == "BOOLEAN":
             ok = {PLAIN, RLE}
         elif self.physical == "INT96":
@@ -731,42 +811,27 @@ class _ColumnDecoder:
         return valid.to(torch.uint8), counts
 
     # -- value decode ------------------------------------------------------
-    def decode(self):
-        self.upload()
-        validity, dense_counts = self.decode_validity()
-        n_dense = sum(dense_counts)
-        ext = _ext()
-        dev = self.device
-
-        # per-page dense row base
-        dense_base = np.cumsum([0] + dense_counts[:-1])
-
-        if self.physical == "BYTE_ARRAY":
-            col = self._decode_strings(ext, validity, dense_counts, dense_base)
-            return col, validity
-
-        # fixed-width physical types; the pages of a column may mix the
-        # row classes plain, dict, delta, byte-stream-split and RLE booleans
+    def _fixed_width(self):
         if self.physical == "FIXED_LEN_BYTE_ARRAY":
-            width, dt = self.flba_w, torch.int64
-        elif self.physical == "BOOLEAN":
-            width, dt = 0, torch.uint8      # bit-packed; one byte per value
-        elif self.physical == "INT96":
-            width, dt = 12, torch.int64     # decoded to epoch microseconds
-        else:
-            width = _PHYS_WIDTH[self.physical]
-            dt = _PHYS_TORCH[self.physical]
-        dense: Optional[torch.Tensor] = None
+            return self.flba_w, torch.int64
+        if self.physical == "BOOLEAN":
+            return 0, torch.uint8           # bit-packed; one byte per value
+        if self.physical == "INT96":
+            return 12, torch.int64          # decoded to epoch microseconds
+        return _PHYS_WIDTH[self.physical], _PHYS_TORCH[self.physical]
 
-        def _out():
-            nonlocal dense
-            if dense is None:
-                dense = torch.empty(n_dense, dtype=dt, device=dev)
-            return dense
-
-        plain_rows, dict_rows, delta_rows, bss_rows, rle_rows = \
-            [], [], [], [], []
+    def _build_tables(self, dense_counts, all_valid) -> Tuple[_Tables, bool]:
+        """Page tables of a fixed-width column, one per row class, from the
+        per-page dense counts. Second value: whether the row loop met a
+        class whose regions it checks against n_values (those tables are
+        rebuilt, and so rechecked, on every scan)."""
+        width, _ = self._fixed_width()
+        dense_base = np.cumsum([0] + dense_counts[:-1])
+        classes = {"plain": [], "dict": [], "delta": [], "bss": [], "rle": []}
+        plain_rows, dict_rows, delta_rows, bss_rows, rle_rows = (
+            classes[k] for k in ("plain", "dict", "delta", "bss", "rle"))
         dict_chunks = []  # (chunk, page row ranges) needing dict values
+        checked = self.physical in ("BOOLEAN", "INT96")
         pi = 0
 
         def _short(what):
@@ -793,12 +858,14 @@ class _ColumnDecoder:
                     delta_rows.append((self._val_off(ch, p), p.val_len,
                                        c, b, 0, 0))
                 elif p.enc == BYTE_STREAM_SPLIT:
+                    checked = True
                     if p.val_len != width * c:
                         raise _short(f"{p.val_len} bytes for {c} "
                                      f"byte-stream-split values of {width}")
                     bss_rows.append((self._val_off(ch, p), p.val_len,
                                      c, b, 0, 0))
                 elif p.enc == RLE:
+                    checked = True
                     # RLE booleans: 4-byte length prefix, then hybrid runs
                     # of width 1. A page of nulls only has no value bytes.
                     if c == 0:
@@ -809,6 +876,56 @@ class _ColumnDecoder:
                         rle_rows.append((self._val_off(ch, p) + 4,
                                          p.val_len - 4, c, b, 0, 1))
                 pi += 1
+        return _Tables(pi, sum(dense_counts), all_valid, classes, dict_chunks,
+                       self.device), checked
+
+    def _tables(self):
+        """(page tables, validity) of this scan. The tables come from the
+        FileIndex when they were built before; the bypasses are columns
+        with compressed chunks (their bases come from the decompress step),
+        columns whose dense counts need a device round trip (v1 pages with
+        nulls and no count in the header) and columns with a length-checked
+        class."""
+        tabs = None if self.compressed else \
+            self.idx._tables.get(self._win_key)
+        if tabs is not None:
+            _TABLE_LRU.move_to_end((id(self.idx), self._win_key))
+            validity = None if tabs.all_valid else self.decode_validity()[0]
+            return tabs, validity
+        validity, dense_counts = self.decode_validity()
+        tabs, checked = self._build_tables(dense_counts, validity is None)
+        if not (self.compressed or checked) and all(
+                p.all_valid or p.ndense is not None for p in self.pages):
+            _remember_tables(self.idx, self._win_key, tabs)
+        return tabs, validity
+
+    def decode(self):
+        self.upload()
+        ext = _ext()
+        dev = self.device
+
+        if self.physical == "BYTE_ARRAY":
+            validity, dense_counts = self.decode_validity()
+            # per-page dense row base
+            dense_base = np.cumsum([0] + dense_counts[:-1])
+            col = self._decode_strings(ext, validity, dense_counts, dense_base)
+            return col, validity
+
+        # fixed-width physical types; the pages of a column may mix the
+        # row classes plain, dict, delta, byte-stream-split and RLE booleans
+        width, dt = self._fixed_width()
+        tabs, validity = self._tables()
+        n_dense, pi = tabs.n_dense, tabs.n_pages
+        plain_rows, dict_rows, delta_rows, bss_rows, rle_rows = (
+            tabs.rows[k] for k in ("plain", "dict", "delta", "bss", "rle"))
+        dict_chunks = tabs.dict_chunks
+        dense: Optional[torch.Tensor] = None
+
+        def _out():
+            nonlocal dense
+            if dense is None:
+                dense = torch.empty(n_dense, dtype=dt, device=dev)
+            return dense
 
         def _place(rows, vals):
             """Rows of one class decoded into `vals` (n_dense long, written
@@ -822,10 +939,10 @@ class _ColumnDecoder:
                 for r in rows:
                     o[r[3]:r[3] + r[2]] = vals[r[3]:r[3] + r[2]]
 
-        if plain_rows:
+        if len(plain_rows):
             # kernels write at out_row (dense row base); the output tensor
             # covers all n_dense rows even when other pages use another enc
-            table = _page_table(plain_rows, dev)
+            table = tabs.dev["plain"]
             if self.physical == "FIXED_LEN_BYTE_ARRAY":
                 _place(plain_rows,
                        ext.pq_flba_i64(self.buf, table, n_dense, width))
@@ -839,29 +956,33 @@ class _ColumnDecoder:
                 raw = ext.pq_plain_copy(self.buf, table, n_dense, width)
                 _place(plain_rows, raw.view(dt))
 
-        if bss_rows:
-            raw = ext.pq_bss_decode(self.buf, _page_table(bss_rows, dev),
-                                    n_dense, width)
+        if len(bss_rows):
+            raw = ext.pq_bss_decode(self.buf, tabs.dev["bss"], n_dense, width)
             _place(bss_rows, raw.view(dt))
 
-        if rle_rows:
-            bits = ext.pq_rle_decode(self.buf, _page_table(rle_rows, dev),
-                                     n_dense)
+        if len(rle_rows):
+            bits = ext.pq_rle_decode(self.buf, tabs.dev["rle"], n_dense)
             _place(rle_rows, bits)
 
-        if delta_rows:
+        if len(delta_rows):
             if self.physical not in ("INT32", "INT64"):
                 raise Unsupported(f"{self.sc.name}: DELTA on {self.physical}")
-            table = _page_table(delta_rows, dev)
-            deltas, _ = ext.pq_delta_decode(
-                self.buf, table,
-                int(np.max([r[3] + r[2] for r in delta_rows])))
-            # finish [first, d1, ...] -> values with the on-device per-page
-            # scan (replaces torch.cumsum + cat + correction gathers)
-            ext.pq_segscan(deltas, table)
-            _place(delta_rows, deltas)
+            table = tabs.dev["delta"]
+            if delta_fused_enabled() and hasattr(ext, "pq_delta_values"):
+                # one pass: packed bytes in, final values of the column's
+                # own width out
+                vals = ext.pq_delta_values(self.buf, table, tabs.delta_total,
+                                           dt == torch.int32)
+            else:
+                vals, _ = ext.pq_delta_decode(self.buf, table,
+                                              tabs.delta_total)
+                # finish [first, d1, ...] -> values with the on-device
+                # per-page scan (replaces torch.cumsum + cat + correction
+                # gathers)
+                ext.pq_segscan(vals, table)
+            _place(delta_rows, vals)
 
-        if dict_rows:
+        if len(dict_rows):
             codes = self._decode_dict_codes(ext, dict_rows)
             o = _out() if dense is None or len(dict_rows) < pi else dense
             if dense is None:

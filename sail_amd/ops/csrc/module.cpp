@@ -45,6 +45,9 @@ torch::Tensor pq_bool_unpack(torch::Tensor buf, torch::Tensor pages, int64_t tot
 torch::Tensor pq_int96_micros(torch::Tensor buf, torch::Tensor pages, int64_t total);
 torch::Tensor pq_bss_decode(torch::Tensor buf, torch::Tensor pages, int64_t total,
                             int64_t width);
+// parquet_delta.hip
+torch::Tensor pq_delta_values(torch::Tensor buf, torch::Tensor pages, int64_t total,
+                              bool as_int32);
 // mfma_reduce.hip
 torch::Tensor mfma_sum_f64(torch::Tensor x, bool use_mfma);
 torch::Tensor pq_gather_strings(torch::Tensor buf, torch::Tensor src_pos,
@@ -93,4 +96,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def(
       "pq_bss_decode", &pq_bss_decode,
       "parquet BYTE_STREAM_SPLIT decode, width 4 or 8");
+  // parquet_delta.hip: case table in tests/test_pq_delta_fused.py
+  m.def(
+      "pq_delta_values", &pq_delta_values,
+      "parquet DELTA_BINARY_PACKED -> final int64/int32 values, one pass");
 }

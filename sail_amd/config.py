@@ -31,6 +31,11 @@ DEFAULTS: Dict[str, str] = {
     # instead of sending the file to the host path; on | off
     # (env SAIL_IO_GPU_SNAPPY, read option gpuSnappy)
     "sail.io.gpu_snappy": "off",
+    # PLAIN byte arrays (plain string pages, string dictionary pages) through
+    # pq_bytearray_index + pq_gather_bytes (ops/csrc/parquet_bytearray.hip);
+    # off = pq_bytearray_walk + pq_gather_strings (env
+    # SAIL_IO_GPU_BYTEARRAY_FAST, read on every decode)
+    "sail.io.gpu_bytearray_fast": "on",
     # kernels
     "sail.kernels.require_on_gpu": "true",
     "sail.kernels.grouped_agg_max_lds_groups": "4096",

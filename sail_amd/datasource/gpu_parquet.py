@@ -11,7 +11,8 @@ Decoded columns are born as device tensors — no pyarrow on the hot path.
 
 Supported: uncompressed v1 and v2 data pages (mixed freely within a
 column), PLAIN fixed-width, PLAIN byte_array, RLE_DICTIONARY (+PLAIN
-dictionary pages), DELTA_BINARY_PACKED, DELTA_LENGTH_BYTE_ARRAY,
+dictionary pages), string columns that fall back from RLE_DICTIONARY to
+PLAIN pages, DELTA_BINARY_PACKED, DELTA_LENGTH_BYTE_ARRAY,
 BYTE_STREAM_SPLIT on INT32/INT64/FLOAT/DOUBLE, BOOLEAN (PLAIN and RLE),
 INT96 timestamps (PLAIN and dictionary; decoded to int64 microseconds),
 FLBA/INT32/INT64 decimals, definition levels (nulls). Anything else raises
@@ -45,6 +46,25 @@ column from two small device->host gathers and cached on the page index.
 A page the kernel rejects (non-zero status) raises Unsupported. Other
 codecs, v2 data pages in a compressed chunk and pages of 2^31 bytes or
 more stay on the host path.
+
+PLAIN byte arrays (plain string pages and every string dictionary page)
+are indexed by pq_bytearray_index and copied by pq_gather_bytes
+(ops/csrc/parquet_bytearray.hip); SAIL_IO_GPU_BYTEARRAY_FAST=off selects
+the older pq_bytearray_walk + pq_gather_strings. pq_bytearray_index checks
+every length against its page and reports a status per page; a page it
+rejects raises Unsupported.
+
+A string column whose dictionary outgrew the writer's limit holds
+RLE_DICTIONARY pages followed by PLAIN pages, within one chunk or across
+the row groups of a window (stock pyarrow, parquet-java and arrow-rs all
+write this for comment, URL, name and address columns). It decodes to the
+plain form StringColumn(offsets, bytes, validity, None): every dense value
+is described as (length, position in the upload), from the length chain
+for PLAIN pages and from the chunk's indexed dictionary page through the
+decoded codes for dictionary pages, and one gather assembles the bytes.
+Such a column carries no dictionary codes, so a later GROUP BY or join on
+it goes through exact string codes; a single-encoding column keeps its
+coded form. A mix that involves DELTA_LENGTH_BYTE_ARRAY is still refused.
 """
 from __future__ import annotations
 
@@ -96,6 +116,32 @@ def delta_fused_enabled() -> bool:
     on every decode, so one process can alternate the two paths."""
     v = os.environ.get("SAIL_IO_GPU_DELTA_FUSED", "on")
     return str(v).lower() not in ("off", "false", "0")
+
+
+def bytearray_fast_enabled() -> bool:
+    """SAIL_IO_GPU_BYTEARRAY_FAST (config sail.io.gpu_bytearray_fast),
+    default on: PLAIN byte arrays go through pq_bytearray_index +
+    pq_gather_bytes. `off`, `0` or `false` selects pq_bytearray_walk +
+    pq_gather_strings. Read on every decode, so one process can alternate
+    the two pairs."""
+    v = os.environ.get("SAIL_IO_GPU_BYTEARRAY_FAST", "on")
+    return str(v).lower() not in ("off", "false", "0")
+
+
+def _check_dict_codes(codes: torch.Tensor, limits: torch.Tensor, name: str):
+    """Raise Unsupported unless 0 <= codes[i] < limits[i] for every i.
+    `limits` holds, per code, the entry count of the dictionary the code
+    indexes. Runs on the device and reads one flag back; callers index
+    with `codes` only after it returns."""
+    if codes.numel() == 0:
+        return
+    c = codes.to(torch.int64)
+    bad = (c < 0) | (c >= limits)
+    if bool(bad.any().item()):
+        i = int(torch.nonzero(bad).flatten()[0].item())
+        raise Unsupported(f"{name}: dictionary code {int(c[i].item())} at "
+                          f"dense value {i} outside a dictionary of "
+                          f"{int(limits[i].item())} entries")
 
 
 #: Cap on the bytes of cached page tables (host array plus device copy) held
@@ -656,7 +702,9 @@ class _ColumnDecoder:
         bad = encs - ok
         if bad:
             raise Unsupported(f"{self.sc.name}: encodings {bad}")
-        if self.physical == "BYTE_ARRAY" and len(encs) > 1:
+        # strings: one encoding, or the dictionary-fallback layout
+        if self.physical == "BYTE_ARRAY" and len(encs) > 1 and \
+                encs != {PLAIN, RLE_DICTIONARY}:
             raise Unsupported(f"{self.sc.name}: mixed string encodings {encs}")
         if self.physical not in ("INT32", "INT64", "FLOAT", "DOUBLE",
                                  "BYTE_ARRAY", "FIXED_LEN_BYTE_ARRAY",
@@ -1035,16 +1083,10 @@ class _ColumnDecoder:
             raise Unsupported(f"{self.sc.name}: dict-encoded page, no dict")
         d_off, d_len = self._dict_region(ch)
         rows = [(d_off, d_len, ch.dict_nvals, 0, 0, 0)]
-        table = _page_table(rows, self.device)
-        lengths, src_pos = ext.pq_bytearray_walk(self.buf, table,
-                                                 ch.dict_nvals)
-        offsets = torch.zeros(ch.dict_nvals + 1, dtype=torch.int64,
-                              device=self.device)
-        torch.cumsum(lengths, 0, out=offsets[1:])
-        total = int(offsets[-1].item())
-        blob = ext.pq_gather_strings(self.buf, src_pos, lengths,
-                                     offsets[:-1], total)
-        return offsets, blob
+        lengths, src_pos, status = self._index_bytearrays(
+            ext, rows, ch.dict_nvals)
+        return self._gather_bytearrays(ext, lengths, src_pos, status,
+                                       lambda i: "dictionary page")
 
     def _dict_values_tensor(self, ch: _Chunk) -> torch.Tensor:
         vals = self._dict_values_host(ch)
@@ -1079,6 +1121,9 @@ class _ColumnDecoder:
         enc = self.pages[0].enc if self.pages else PLAIN
         dev = self.device
         n_dense = sum(dense_counts)
+        if any(p.enc != enc for p in self.pages):
+            return self._decode_mixed_strings(ext, validity, dense_counts,
+                                              dense_base)
         if enc == RLE_DICTIONARY:
             dict_rows = []
             pi = 0
@@ -1197,13 +1242,122 @@ class _ColumnDecoder:
                 rows.append((self._val_off(ch, p), p.val_len,
                              dense_counts[pi], int(dense_base[pi]), 0, 0))
                 pi += 1
-        lengths, src_pos = ext.pq_bytearray_walk(
-            self.buf, _page_table(rows, dev), n_dense)
-        offsets = torch.zeros(n_dense + 1, dtype=torch.int64, device=dev)
+        lengths, src_pos, status = self._index_bytearrays(ext, rows, n_dense)
+        offsets, blob = self._gather_bytearrays(
+            ext, lengths, src_pos, status, lambda i: f"page {i} of {len(rows)}")
+        return self._assemble_strings(offsets, blob, lengths, validity,
+                                      dense_counts)
+
+    def _index_bytearrays(self, ext, rows, total):
+        """PLAIN byte-array regions of self.buf -> (lengths, src_pos,
+        per-region status or None): pq_bytearray_index, or
+        pq_bytearray_walk (which checks nothing and has no status) when the
+        switch is off or the extension lacks the new entry point."""
+        table = _page_table(rows, self.device)
+        if bytearray_fast_enabled() and hasattr(ext, "pq_bytearray_index"):
+            lengths, src_pos, status = ext.pq_bytearray_index(
+                self.buf, table, total)
+            return lengths, src_pos, status
+        lengths, src_pos = ext.pq_bytearray_walk(self.buf, table, total)
+        return lengths, src_pos, None
+
+    def _gather_bytearrays(self, ext, lengths, src_pos, status, what):
+        """(offsets int64[n+1], bytes u8) of values described by length
+        and position in self.buf: one cumsum, one device->host read (the
+        byte total and, with a status, the count of rejected regions), one
+        gather. A rejected region raises Unsupported; what(i) names region
+        i of the status."""
+        n = lengths.numel()
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
         torch.cumsum(lengths, 0, out=offsets[1:])
-        total_bytes = int(offsets[-1].item())
-        blob = ext.pq_gather_strings(self.buf, src_pos, lengths,
-                                     offsets[:-1], total_bytes)
+        if status is not None and status.numel():
+            total, nbad = torch.stack(
+                [offsets[-1], (status != 0).sum()]).tolist()
+            if nbad:
+                i = int(torch.nonzero(status).flatten()[0].item())
+                raise Unsupported(
+                    f"{self.sc.name}: {what(i)} rejected, status "
+                    f"{int(status[i].item())}")
+        else:
+            total = int(offsets[-1].item())
+        if bytearray_fast_enabled() and hasattr(ext, "pq_gather_bytes"):
+            blob = ext.pq_gather_bytes(self.buf, src_pos, lengths,
+                                       offsets[:-1], total)
+        else:
+            blob = ext.pq_gather_strings(self.buf, src_pos, lengths,
+                                         offsets[:-1], total)
+        return offsets, blob
+
+    def _decode_mixed_strings(self, ext, validity, dense_counts, dense_base):
+        """RLE_DICTIONARY and PLAIN pages in one column (the writer's
+        dictionary overflowed): every dense value becomes (length, position
+        in self.buf), then one gather. The result is a plain StringColumn,
+        without codes."""
+        dev = self.device
+        n_dense = sum(dense_counts)
+        plain_rows, dict_rows = [], []
+        page_chunk = []     # per dictionary-encoded page: index of its chunk
+        pi = 0
+        for ci, ch in enumerate(self.chunks):
+            for p in ch.pages:
+                row = (self._val_off(ch, p), p.val_len, dense_counts[pi],
+                       int(dense_base[pi]), 0, 0)
+                if p.enc == PLAIN:
+                    plain_rows.append(row)
+                else:
+                    dict_rows.append(row[:5] + (p.bw0,))
+                    page_chunk.append(ci)
+                pi += 1
+        # PLAIN pages write their dense rows; the rest stay (0, 0)
+        lengths, src_pos, status = self._index_bytearrays(
+            ext, plain_rows, n_dense)
+        n_plain = len(plain_rows)
+        used = sorted(set(page_chunk))   # chunks with dictionary-coded pages
+
+        def what(i):
+            if i < n_plain:
+                return f"plain page {i} of {n_plain}"
+            return f"dictionary page of row group {used[i - n_plain]}"
+
+        n_codes = sum(r[2] for r in dict_rows)
+        if n_codes:
+            codes = self._decode_dict_codes(ext, dict_rows)
+            # one index launch over the dictionary pages of the chunks that
+            # use them; chunk ci's entries start at ent_base[ci]
+            ent_base, ent_rows, at = {}, [], 0
+            for ci in used:
+                ch = self.chunks[ci]
+                if ch.dict_off is None:
+                    raise Unsupported(
+                        f"{self.sc.name}: dict-encoded page, no dict")
+                d_off, d_len = self._dict_region(ch)
+                ent_rows.append((d_off, d_len, ch.dict_nvals, at, 0, 0))
+                ent_base[ci] = at
+                at += ch.dict_nvals
+            ent_len, ent_src, ent_status = self._index_bytearrays(
+                ext, ent_rows, at)
+            # per code: its dictionary's size and base, and its dense row
+            per_page = torch.tensor(
+                [[self.chunks[ci].dict_nvals for ci in page_chunk],
+                 [ent_base[ci] for ci in page_chunk],
+                 [r[3] for r in dict_rows],
+                 np.cumsum([0] + [r[2] for r in dict_rows[:-1]]).tolist()],
+                dtype=torch.int64, device=dev)
+            counts = torch.tensor([r[2] for r in dict_rows],
+                                  dtype=torch.int64, device=dev)
+            page_of = torch.repeat_interleave(
+                torch.arange(len(dict_rows), device=dev), counts,
+                output_size=n_codes)
+            limit, base, row0, code0 = per_page.index_select(1, page_of)
+            _check_dict_codes(codes, limit, self.sc.name)
+            entry = codes.to(torch.int64) + base
+            dest = row0 + (torch.arange(n_codes, device=dev) - code0)
+            lengths[dest] = ent_len.index_select(0, entry)
+            src_pos[dest] = ent_src.index_select(0, entry)
+            if ent_status is not None:
+                status = torch.cat([status, ent_status])
+        offsets, blob = self._gather_bytearrays(ext, lengths, src_pos, status,
+                                                what)
         return self._assemble_strings(offsets, blob, lengths, validity,
                                       dense_counts)
 

@@ -48,6 +48,12 @@ torch::Tensor pq_bss_decode(torch::Tensor buf, torch::Tensor pages, int64_t tota
 // parquet_delta.hip
 torch::Tensor pq_delta_values(torch::Tensor buf, torch::Tensor pages, int64_t total,
                               bool as_int32);
+// parquet_bytearray.hip
+std::vector<torch::Tensor> pq_bytearray_index(torch::Tensor buf, torch::Tensor pages,
+                                              int64_t total);
+torch::Tensor pq_gather_bytes(torch::Tensor buf, torch::Tensor src_pos,
+                              torch::Tensor lengths, torch::Tensor out_offsets,
+                              int64_t total_bytes);
 // mfma_reduce.hip
 torch::Tensor mfma_sum_f64(torch::Tensor x, bool use_mfma);
 torch::Tensor pq_gather_strings(torch::Tensor buf, torch::Tensor src_pos,
@@ -100,4 +106,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def(
       "pq_delta_values", &pq_delta_values,
       "parquet DELTA_BINARY_PACKED -> final int64/int32 values, one pass");
+  // parquet_bytearray.hip: case table in tests/test_pq_bytearray_kernels.py
+  m.def(
+      "pq_bytearray_index", &pq_bytearray_index,
+      "parquet PLAIN byte_array length chain -> lengths, positions, page status");
+  m.def(
+      "pq_gather_bytes", &pq_gather_bytes,
+      "gather byte_array payloads, work divided by output bytes");
 }

@@ -15,7 +15,12 @@
 // (definition levels, RLE_DICTIONARY indices), DELTA_BINARY_PACKED,
 // DELTA_LENGTH_BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY decimals. PLAIN BOOLEAN,
 // PLAIN INT96 and BYTE_STREAM_SPLIT are in parquet_types.hip; RLE booleans
-// are hybrid runs of width 1 and use rle_decode_kernel.
+// are hybrid runs of width 1 and use rle_decode_kernel. PLAIN byte_array
+// pages and string dictionary pages go through parquet_bytearray.hip
+// (pq_bytearray_index, pq_gather_bytes) unless sail.io.gpu_bytearray_fast
+// is off; bytearray_walk_kernel and gather_strings_kernel below are the
+// older pair. A string column that falls back from RLE_DICTIONARY to PLAIN
+// pages is decoded from both kinds of page (datasource/gpu_parquet.py).
 // The kernels see value and level regions only, so v1 and v2 data pages
 // look the same to them (the host finds the regions). SNAPPY v1 pages are
 // expanded first by snappy.hip when sail.io.gpu_snappy is on. Still on the
@@ -401,8 +406,10 @@ __global__ void segscan_kernel(long* __restrict__ data,
 }
 
 // ---------------------------------------------------------------------------
-// PLAIN BYTE_ARRAY: sequential <u32 len><bytes> walk (compat path; the
-// bench writer uses DELTA_LENGTH_BYTE_ARRAY which decodes fully parallel)
+// PLAIN BYTE_ARRAY: sequential <u32 len><bytes> walk and one-thread-per-
+// value copy. The older pair, kept behind sail.io.gpu_bytearray_fast=off:
+// the walk checks no length against its page and leaves the rows of a
+// truncated page unwritten (parquet_bytearray.hip does both)
 // ---------------------------------------------------------------------------
 __global__ void bytearray_walk_kernel(const uint8_t* __restrict__ buf,
                                       const long* __restrict__ pages, int npages,

@@ -532,7 +532,9 @@ def _commit_snapshot(t: "IcebergTable", md: dict, manifests: List[dict],
                      operation: str):
     """Write manifest list + snapshot entry + new vN.metadata.json
     (the tail every commit shares; ref: sail-iceberg commit flow)."""
-    now_ms = int(time.time() * 1000)
+    # two commits inside one millisecond must not share a timestamp: time
+    # travel by as-of-timestamp picks the latest snapshot at or before it
+    now_ms = max(int(time.time() * 1000), md.get("last-updated-ms", 0) + 1)
     ml_path = os.path.join(t.meta_dir, f"snap-{snap_id}.avro")
     write_container(ml_path, _MANIFEST_FILE_SCHEMA, manifests, metadata={
         "snapshot-id": str(snap_id).encode(),

@@ -511,8 +511,11 @@ def _f_substring(args, out, chunk, ev):
 
         offs, byts = _pack_strings(vals, c.device)
         return StringColumn(offs, byts, c.validity, c.codes)
-    if isinstance(c, StringColumn) and c.is_cuda and s >= 1 and ln is not None:
-        # device kernel: fixed-pitch extraction then compaction (all on GPU)
+    if (isinstance(c, StringColumn) and c.is_cuda and s >= 1 and ln is not None
+            and ln >= 1 and not bool((c.bytes_ >= 0x80).any())):
+        # device kernel: fixed-pitch extraction then compaction (all on GPU).
+        # The kernel counts bytes, substring counts characters: the two agree
+        # on ASCII only, so a column with a byte >= 0x80 takes the host path.
         from ..ops import kernels as K
 
         buf, lens = K.require().substr_fixed(c.offsets, c.bytes_, s - 1, ln)
@@ -560,9 +563,10 @@ def _str_pred(fn):
             raise NotImplementedError("string predicate with column pattern")
         p = pat.value
         if isinstance(c, StringColumn) and c.is_dict:
-            if c.is_cuda and "%" not in p and "_" not in p:
+            if c.is_cuda:
                 from ..ops import kernels as K
 
+                p = K.like_escape(p)
                 like_pat = {"startswith": p + "%", "endswith": "%" + p,
                             "contains": "%" + p + "%"}[fn.__name__]
                 hit = K.require().like_mask(c.offsets, c.bytes_, like_pat.encode())

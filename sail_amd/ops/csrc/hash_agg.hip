@@ -9,7 +9,9 @@
 //    scratch, guide rule #20), then a block reduction through LDS and one
 //    global atomic per (block, group, column).
 //  * grouped_acc_lds   (G <= 4096): LDS accumulator table with LDS atomics,
-//    flushed once per block. 160 KB LDS/CU covers 4096 groups x 4 columns.
+//    flushed once per block. Of the 160 KB LDS/CU the table takes up to
+//    2048 groups x 10 columns, or 4096 groups x 4 columns (128 KB, the
+//    engine's largest launch); wider launches above 2048 groups are refused.
 //
 // Larger G falls back to torch index_add_ (scattered global atomics are
 // fine once contention is low).
@@ -35,7 +37,7 @@ inline int grid_for_n(int64_t n, int per_thread = 16) {
 struct ColArg {
   const void* ptr;   // value column (elem type per tag) or null for count
   int op;            // 0 sum_i64, 1 sum_f64, 2 count, 3 min_i64, 4 max_i64
-  int elem;          // 0 i64, 1 f64, 2 i32, 3 f32, 4 u8/bool
+  int elem;          // 0 i64, 1 f64, 2 i32, 3 f32, 4 u8/bool, 5 i16, 6 i8
 };
 
 __device__ inline long long load_as_i64(const void* p, int elem, int64_t i) {
@@ -55,6 +57,7 @@ __device__ inline double load_as_f64(const void* p, int elem, int64_t i) {
     case 3: return (double)((const float*)p)[i];
     case 0: return (double)((const long long*)p)[i];
     case 2: return (double)((const int*)p)[i];
+    case 4: return (double)((const uint8_t*)p)[i];
     case 5: return (double)((const short*)p)[i];
     case 6: return (double)((const int8_t*)p)[i];
     default: return 0.0;
@@ -219,13 +222,19 @@ __global__ void grouped_acc_lds(const int32_t* __restrict__ gid,
   }
 }
 
-ColArg make_col(const c10::optional<torch::Tensor>& t, int op) {
+ColArg make_col(const c10::optional<torch::Tensor>& t, int op, int64_t n) {
   ColArg a;
   a.op = op;
   a.ptr = nullptr;
   a.elem = 0;
-  if (t.has_value() && t->defined()) {
+  TORCH_CHECK(op >= 0 && op <= 4, "grouped_acc: unknown op ", op);
+  bool has = t.has_value() && t->defined();
+  // only a count reads no values; every other op dereferences the column
+  TORCH_CHECK(has || op == 2, "grouped_acc: op ", op, " needs a value column");
+  if (has) {
     auto& x = *t;
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.numel() == n,
+                "grouped_acc: value columns must be contiguous cuda tensors of gid's length");
     a.ptr = x.data_ptr();
     switch (x.scalar_type()) {
       case torch::kInt64: a.elem = 0; break;
@@ -238,8 +247,19 @@ ColArg make_col(const c10::optional<torch::Tensor>& t, int op) {
       case torch::kInt8: a.elem = 6; break;
       default: TORCH_CHECK(false, "unsupported value dtype for grouped_acc");
     }
+    // integer sum/min/max accumulate in int64 and have no float load: refuse
+    // rather than let the kernel read such a column as zeros
+    TORCH_CHECK(!((op == 0 || op == 3 || op == 4) && (a.elem == 1 || a.elem == 3)),
+                "grouped_acc: op ", op, " cannot take a floating-point column");
   }
   return a;
+}
+
+// a refused launch must raise: `out` is zero-initialised and would otherwise
+// be returned as the answer
+void check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, what, " launch failed: ", hipGetErrorString(e));
 }
 
 }  // namespace
@@ -253,6 +273,30 @@ torch::Tensor grouped_acc(torch::Tensor gid, c10::optional<torch::Tensor> mask,
   int64_t n = gid.numel();
   int ncols = (int)vals.size();
   TORCH_CHECK(ncols >= 1 && ncols <= 10, "1..10 columns per launch");
+  TORCH_CHECK((int)ops.size() == ncols, "grouped_acc: one op per column");
+  TORCH_CHECK(G >= 1, "grouped_acc: G must be positive");
+  // every refusal comes before any allocation or launch
+  bool tiny_ok = G <= 8;
+  for (int c = 0; c < ncols && tiny_ok; ++c)
+    if (ops[c] == 3 || ops[c] == 4) tiny_ok = false;
+  size_t lds_bytes = (size_t)ncols * G * 8;
+  if (!tiny_ok) {
+    TORCH_CHECK(G <= 4096, "grouped_acc: G too large for LDS variant");
+    // 160 KB of LDS: up to 10 columns at 2048 groups; above that the table
+    // is sized for the engine's own launches of at most 4 columns
+    TORCH_CHECK(lds_bytes <= 160 * 1024 && (G <= 2048 || ncols <= 4),
+                "grouped_acc: LDS budget exceeded");
+  }
+  ColArg cols[10];
+  for (int c = 0; c < 10; ++c)
+    cols[c] = make_col(c < ncols ? vals[c] : c10::nullopt, c < ncols ? (int)ops[c] : 2, n);
+  const uint8_t* mptr = nullptr;
+  if (mask.has_value() && mask->defined()) {
+    TORCH_CHECK(mask->scalar_type() == torch::kBool || mask->scalar_type() == torch::kUInt8);
+    TORCH_CHECK(mask->is_cuda() && mask->is_contiguous() && mask->numel() == n,
+                "grouped_acc: mask must be a contiguous cuda tensor of gid's length");
+    mptr = (const uint8_t*)mask->data_ptr();
+  }
   auto out = torch::zeros({ncols, G}, gid.options().dtype(torch::kInt64));
   // min/max initialization
   for (int c = 0; c < ncols; ++c) {
@@ -260,18 +304,7 @@ torch::Tensor grouped_acc(torch::Tensor gid, c10::optional<torch::Tensor> mask,
     if (ops[c] == 4) out[c].fill_(INT64_MIN);
   }
   if (n == 0) return out;
-  ColArg cols[10];
-  for (int c = 0; c < 10; ++c)
-    cols[c] = make_col(c < ncols ? vals[c] : c10::nullopt, c < ncols ? (int)ops[c] : 0);
-  const uint8_t* mptr = nullptr;
-  if (mask.has_value() && mask->defined()) {
-    TORCH_CHECK(mask->scalar_type() == torch::kBool || mask->scalar_type() == torch::kUInt8);
-    mptr = (const uint8_t*)mask->data_ptr();
-  }
   hipStream_t stream = c10::hip::getCurrentHIPStream();
-  bool tiny_ok = G <= 8;
-  for (int c = 0; c < ncols && tiny_ok; ++c)
-    if (ops[c] == 3 || ops[c] == 4) tiny_ok = false;
   if (tiny_ok) {
     // TG matched to the actual group count: acc[NC][TG] lives in VGPRs, so
     // TG=8 for G=4 (q1) doubles register pressure for nothing and costs
@@ -295,15 +328,14 @@ torch::Tensor grouped_acc(torch::Tensor gid, c10::optional<torch::Tensor> mask,
     }
 #undef TINY_CASE
 #undef TINY_LAUNCH
+    check_launch("grouped_acc_tiny");
     return out;
   }
-  TORCH_CHECK(G <= 4096, "grouped_acc: G too large for LDS variant");
-  size_t lds_bytes = (size_t)ncols * G * 8;
-  TORCH_CHECK(lds_bytes <= 160 * 1024, "grouped_acc: LDS budget exceeded");
   int grid = grid_for_n(n, 8);
   hipLaunchKernelGGL(grouped_acc_lds, dim3(grid), dim3(kBlock), lds_bytes, stream,
                      gid.data_ptr<int32_t>(), mptr, n, cols[0], cols[1], cols[2],
                      cols[3], cols[4], cols[5], cols[6], cols[7], cols[8], cols[9],
                      ncols, out.data_ptr<int64_t>(), (int)G);
+  check_launch("grouped_acc_lds");
   return out;
 }

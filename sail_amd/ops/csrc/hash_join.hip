@@ -37,28 +37,57 @@ __device__ inline uint64_t mix64(uint64_t k) {
   return k;
 }
 
+// Table layout: slots [0, tmask] are the open-addressing area; slot tmask+1
+// belongs to the one key whose bit pattern equals the empty marker. That key
+// cannot be stored as itself, and remapping it onto a neighbouring value
+// would merge it with a live key (the null sentinels of the join are such
+// neighbours), so it gets a slot of its own, marked taken with kTaken.
+constexpr long long kTaken = 0;
+
+// Find or claim the slot of `k`; *first is set for the thread that claimed it.
+__device__ inline int64_t claim_slot(int64_t* __restrict__ tkeys, long long k,
+                                     int64_t tmask, bool* first) {
+  if (k == kEmpty) {
+    long long prev = atomicCAS((unsigned long long*)&tkeys[tmask + 1],
+                               (unsigned long long)kEmpty, (unsigned long long)kTaken);
+    *first = (prev == kEmpty);
+    return tmask + 1;
+  }
+  uint64_t h = mix64((uint64_t)k) & tmask;
+  while (true) {
+    long long prev = atomicCAS((unsigned long long*)&tkeys[h],
+                               (unsigned long long)kEmpty, (unsigned long long)k);
+    if (prev == kEmpty || prev == k) {
+      *first = (prev == kEmpty);
+      return (int64_t)h;
+    }
+    h = (h + 1) & tmask;
+  }
+}
+
+// Slot of `k` in a finished table, or -1 when the key is absent.
+__device__ inline int64_t find_slot(const int64_t* __restrict__ tkeys, long long k,
+                                    int64_t tmask) {
+  if (k == kEmpty) return tkeys[tmask + 1] == kEmpty ? -1 : tmask + 1;
+  uint64_t h = mix64((uint64_t)k) & tmask;
+  while (true) {
+    long long tk = tkeys[h];
+    if (tk == kEmpty) return -1;
+    if (tk == k) return (int64_t)h;
+    h = (h + 1) & tmask;
+  }
+}
+
 __global__ void hj_build_kernel(const int64_t* __restrict__ keys, int64_t n,
                                 int64_t* __restrict__ tkeys,
                                 int64_t* __restrict__ tvals, int64_t tmask,
                                 int* __restrict__ dup_flag) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += gridDim.x * (int64_t)blockDim.x) {
-    long long k = keys[i];
-    if (k == kEmpty) k = kEmpty + 1;  // remap the reserved marker
-    uint64_t h = mix64((uint64_t)k) & tmask;
-    while (true) {
-      long long prev = atomicCAS((unsigned long long*)&tkeys[h],
-                                 (unsigned long long)kEmpty, (unsigned long long)k);
-      if (prev == kEmpty) {
-        tvals[h] = i;
-        break;
-      }
-      if (prev == k) {
-        *dup_flag = 1;  // duplicate key: keep first, flag for caller
-        break;
-      }
-      h = (h + 1) & tmask;
-    }
+    bool first;
+    int64_t h = claim_slot(tkeys, keys[i], tmask, &first);
+    if (first) tvals[h] = i;
+    else *dup_flag = 1;  // duplicate key: keep first, flag for caller
   }
 }
 
@@ -69,27 +98,14 @@ __global__ void hj_probe_unique_kernel(const int64_t* __restrict__ keys, int64_t
                                        int64_t* __restrict__ out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += gridDim.x * (int64_t)blockDim.x) {
-    long long k = keys[i];
-    if (k == kEmpty) k = kEmpty + 1;
-    uint64_t h = mix64((uint64_t)k) & tmask;
-    int64_t r = -1;
-    while (true) {
-      long long tk = tkeys[h];
-      if (tk == kEmpty) break;
-      if (tk == k) {
-        r = tvals[h];
-        break;
-      }
-      h = (h + 1) & tmask;
-    }
-    out[i] = r;
+    int64_t h = find_slot(tkeys, keys[i], tmask);
+    out[i] = h >= 0 ? tvals[h] : -1;
   }
 }
 
-// duplicate-key build: chain layout. tvals holds the FIRST build row for the
-// key; `next[row]` links further rows with the same key (built by a second
-// pass in insertion order — order within a key is arbitrary, as in any hash
-// join).
+// duplicate-key build: chain layout. theads holds the LAST inserted build row
+// for the key; `next[row]` links further rows with the same key (order within
+// a key is arbitrary, as in any hash join).
 __global__ void hj_chain_kernel(const int64_t* __restrict__ keys, int64_t n,
                                 int64_t* __restrict__ tkeys,
                                 int64_t* __restrict__ theads, int64_t tmask,
@@ -97,21 +113,11 @@ __global__ void hj_chain_kernel(const int64_t* __restrict__ keys, int64_t n,
   // push-front chains: head[slot] <- row with next[row] = old head
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += gridDim.x * (int64_t)blockDim.x) {
-    long long k = keys[i];
-    if (k == kEmpty) k = kEmpty + 1;
-    uint64_t h = mix64((uint64_t)k) & tmask;
-    while (true) {
-      long long prev = atomicCAS((unsigned long long*)&tkeys[h],
-                                 (unsigned long long)kEmpty, (unsigned long long)k);
-      if (prev == kEmpty || prev == k) {
-        // claim slot for this key (first claimer) or found the key's slot
-        long long old = atomicExch((unsigned long long*)&theads[h],
-                                   (unsigned long long)i);
-        next[i] = old;  // old == -1 for first
-        break;
-      }
-      h = (h + 1) & tmask;
-    }
+    bool first;  // unused: the head exchange orders the chain by itself
+    int64_t h = claim_slot(tkeys, keys[i], tmask, &first);
+    long long old = atomicExch((unsigned long long*)&theads[h],
+                               (unsigned long long)i);
+    next[i] = old;  // old == -1 for first
   }
 }
 
@@ -123,19 +129,10 @@ __global__ void hj_probe_count_kernel(const int64_t* __restrict__ keys, int64_t 
                                       int32_t* __restrict__ counts) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += gridDim.x * (int64_t)blockDim.x) {
-    long long k = keys[i];
-    if (k == kEmpty) k = kEmpty + 1;
-    uint64_t h = mix64((uint64_t)k) & tmask;
+    int64_t h = find_slot(tkeys, keys[i], tmask);
     int c = 0;
-    while (true) {
-      long long tk = tkeys[h];
-      if (tk == kEmpty) break;
-      if (tk == k) {
-        for (int64_t r = theads[h]; r >= 0; r = next[r]) ++c;
-        break;
-      }
-      h = (h + 1) & tmask;
-    }
+    if (h >= 0)
+      for (int64_t r = theads[h]; r >= 0; r = next[r]) ++c;
     counts[i] = c;
   }
 }
@@ -150,22 +147,13 @@ __global__ void hj_probe_fill_kernel(const int64_t* __restrict__ keys, int64_t n
                                      int64_t* __restrict__ out_build) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += gridDim.x * (int64_t)blockDim.x) {
-    long long k = keys[i];
-    if (k == kEmpty) k = kEmpty + 1;
-    uint64_t h = mix64((uint64_t)k) & tmask;
+    int64_t h = find_slot(tkeys, keys[i], tmask);
+    if (h < 0) continue;
     int64_t o = offsets[i];
-    while (true) {
-      long long tk = tkeys[h];
-      if (tk == kEmpty) break;
-      if (tk == k) {
-        for (int64_t r = theads[h]; r >= 0; r = next[r]) {
-          out_probe[o] = i;
-          out_build[o] = r;
-          ++o;
-        }
-        break;
-      }
-      h = (h + 1) & tmask;
+    for (int64_t r = theads[h]; r >= 0; r = next[r]) {
+      out_probe[o] = i;
+      out_build[o] = r;
+      ++o;
     }
   }
 }
@@ -174,6 +162,14 @@ int64_t table_size_for(int64_t n) {
   int64_t sz = 64;
   while (sz < 2 * n) sz <<= 1;
   return sz;
+}
+
+// tables are allocated with sz + 1 slots (see claim_slot); the probe entry
+// points recover the mask from the tensor they are handed
+int64_t tmask_of(const torch::Tensor& tkeys) {
+  int64_t sz = tkeys.numel() - 1;
+  TORCH_CHECK(sz >= 64 && (sz & (sz - 1)) == 0, "not a hash table built by hj_build*");
+  return sz - 1;
 }
 
 // ------------------------------------------------------------------
@@ -191,23 +187,10 @@ __global__ void hg_claim_kernel(const int64_t* __restrict__ keys, int64_t n,
                                 int64_t* __restrict__ slot_of_row) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += gridDim.x * (int64_t)blockDim.x) {
-    long long k = keys[i];
-    if (k == kEmpty) k = kEmpty + 1;
-    uint64_t h = mix64((uint64_t)k) & tmask;
-    while (true) {
-      long long prev = atomicCAS((unsigned long long*)&tkeys[h],
-                                 (unsigned long long)kEmpty, (unsigned long long)k);
-      if (prev == kEmpty) {
-        trow[h] = i;  // claim winner records the representative row
-        slot_of_row[i] = h;
-        break;
-      }
-      if (prev == k) {
-        slot_of_row[i] = h;
-        break;
-      }
-      h = (h + 1) & tmask;
-    }
+    bool first;
+    int64_t h = claim_slot(tkeys, keys[i], tmask, &first);
+    if (first) trow[h] = i;  // claim winner records the representative row
+    slot_of_row[i] = h;
   }
 }
 
@@ -232,8 +215,8 @@ std::vector<torch::Tensor> hj_build(torch::Tensor keys) {
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
   int64_t n = keys.numel();
   int64_t sz = table_size_for(std::max<int64_t>(n, 1));
-  auto tkeys = torch::full({sz}, kEmpty, keys.options());
-  auto tvals = torch::empty({sz}, keys.options());
+  auto tkeys = torch::full({sz + 1}, kEmpty, keys.options());
+  auto tvals = torch::empty({sz + 1}, keys.options());
   auto dup = torch::zeros({1}, keys.options().dtype(torch::kInt32));
   if (n) {
     hipStream_t stream = c10::hip::getCurrentHIPStream();
@@ -253,7 +236,7 @@ torch::Tensor hj_probe_unique(torch::Tensor tkeys, torch::Tensor tvals,
     hipLaunchKernelGGL(hj_probe_unique_kernel, dim3(grid_for(n)), dim3(kBlock), 0,
                        stream, keys.data_ptr<int64_t>(), n,
                        tkeys.data_ptr<int64_t>(), tvals.data_ptr<int64_t>(),
-                       tkeys.numel() - 1, out.data_ptr<int64_t>());
+                       tmask_of(tkeys), out.data_ptr<int64_t>());
   }
   return out;
 }
@@ -262,8 +245,8 @@ std::vector<torch::Tensor> hj_build_chain(torch::Tensor keys) {
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
   int64_t n = keys.numel();
   int64_t sz = table_size_for(std::max<int64_t>(n, 1));
-  auto tkeys = torch::full({sz}, kEmpty, keys.options());
-  auto theads = torch::full({sz}, -1, keys.options());
+  auto tkeys = torch::full({sz + 1}, kEmpty, keys.options());
+  auto theads = torch::full({sz + 1}, -1, keys.options());
   auto next = torch::empty({std::max<int64_t>(n, 1)}, keys.options());
   if (n) {
     hipStream_t stream = c10::hip::getCurrentHIPStream();
@@ -283,7 +266,7 @@ torch::Tensor hj_probe_count(torch::Tensor tkeys, torch::Tensor theads,
     hipLaunchKernelGGL(hj_probe_count_kernel, dim3(grid_for(n)), dim3(kBlock), 0,
                        stream, keys.data_ptr<int64_t>(), n,
                        tkeys.data_ptr<int64_t>(), theads.data_ptr<int64_t>(),
-                       next.data_ptr<int64_t>(), tkeys.numel() - 1,
+                       next.data_ptr<int64_t>(), tmask_of(tkeys),
                        counts.data_ptr<int32_t>());
   }
   return counts;
@@ -300,7 +283,7 @@ std::vector<torch::Tensor> hj_probe_fill(torch::Tensor tkeys, torch::Tensor thea
     hipLaunchKernelGGL(hj_probe_fill_kernel, dim3(grid_for(n)), dim3(kBlock), 0,
                        stream, keys.data_ptr<int64_t>(), n,
                        tkeys.data_ptr<int64_t>(), theads.data_ptr<int64_t>(),
-                       next.data_ptr<int64_t>(), tkeys.numel() - 1,
+                       next.data_ptr<int64_t>(), tmask_of(tkeys),
                        offsets.data_ptr<int64_t>(), out_probe.data_ptr<int64_t>(),
                        out_build.data_ptr<int64_t>());
   }
@@ -312,10 +295,10 @@ std::vector<torch::Tensor> hg_group(torch::Tensor keys) {
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);
   int64_t n = keys.numel();
   int64_t sz = table_size_for(std::max<int64_t>(n, 1));
-  auto tkeys = torch::full({sz}, kEmpty, keys.options());
-  auto trow = torch::empty({sz}, keys.options());
+  auto tkeys = torch::full({sz + 1}, kEmpty, keys.options());
+  auto trow = torch::empty({sz + 1}, keys.options());
   auto slot_of_row = torch::empty({std::max<int64_t>(n, 1)}, keys.options());
-  auto slot_ids = torch::empty({sz}, keys.options().dtype(torch::kInt32));
+  auto slot_ids = torch::empty({sz + 1}, keys.options().dtype(torch::kInt32));
   auto rep = torch::empty({std::max<int64_t>(n, 1)}, keys.options());
   auto counter = torch::zeros({1}, keys.options().dtype(torch::kInt32));
   if (n) {
@@ -324,8 +307,8 @@ std::vector<torch::Tensor> hg_group(torch::Tensor keys) {
                        keys.data_ptr<int64_t>(), n, tkeys.data_ptr<int64_t>(),
                        trow.data_ptr<int64_t>(), sz - 1,
                        slot_of_row.data_ptr<int64_t>());
-    hipLaunchKernelGGL(hg_scan_kernel, dim3(grid_for(sz)), dim3(kBlock), 0, stream,
-                       tkeys.data_ptr<int64_t>(), trow.data_ptr<int64_t>(), sz,
+    hipLaunchKernelGGL(hg_scan_kernel, dim3(grid_for(sz + 1)), dim3(kBlock), 0, stream,
+                       tkeys.data_ptr<int64_t>(), trow.data_ptr<int64_t>(), sz + 1,
                        slot_ids.data_ptr<int32_t>(), rep.data_ptr<int64_t>(),
                        counter.data_ptr<int32_t>());
   }

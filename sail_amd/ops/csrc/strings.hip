@@ -2,7 +2,7 @@
 //
 // Device-side operations over Arrow-layout string columns
 // (offsets int64[n+1], bytes uint8[total]):
-//   like_mask      — SQL LIKE ('%', '_') per row -> bool mask
+//   like_mask      — SQL LIKE ('%', '_', '\' escapes) per row -> bool mask
 //   string_hash64  — FNV-1a 64-bit per row (grouping/join keys for raw
 //                    strings; dictionary-encoded columns never need this)
 //   substr_fixed   — substring(start,len) into a fixed-pitch buffer
@@ -32,17 +32,35 @@ inline int grid_for(int64_t n) {
 
 __device__ inline bool like_match(const uint8_t* s, int64_t slen,
                                   const uint8_t* p, int plen) {
-  // iterative wildcard match with single backtrack point ('%')
+  // iterative wildcard match with single backtrack point ('%').
+  // '%' in the pattern is always the wildcard (tested before literal
+  // equality, so a '%' byte in the string cannot consume it); '\x' is the
+  // literal byte x, as in the host's like_to_regex; a trailing lone '\' is
+  // a literal backslash.
   int64_t si = 0, ss = 0;
   int pi = 0, star = -1;
   while (si < slen) {
-    if (pi < plen && (p[pi] == '_' || p[pi] == s[si])) {
-      ++si;
-      ++pi;
-    } else if (pi < plen && p[pi] == '%') {
+    if (pi < plen && p[pi] == '%') {
       star = pi++;
       ss = si;
-    } else if (star >= 0) {
+      continue;
+    }
+    if (pi < plen) {
+      uint8_t c = p[pi];
+      int adv = 1;
+      bool wild = (c == '_');
+      if (c == '\\' && pi + 1 < plen) {
+        c = p[pi + 1];
+        adv = 2;
+        wild = false;
+      }
+      if (wild || c == s[si]) {
+        ++si;
+        pi += adv;
+        continue;
+      }
+    }
+    if (star >= 0) {
       pi = star + 1;
       si = ++ss;
     } else {
@@ -86,8 +104,10 @@ __device__ inline int64_t find_from(const uint8_t* s, int64_t len,
       int64_t cand = j + pos;
       z &= z - 1ull;  // clear lowest set bit's byte marker
       if (cand > last) return -1;
+      // the zero-byte trick also flags the byte c0^1 right after a true c0
+      // (the borrow carries into it), so byte 0 is compared as well
       bool ok = true;
-      for (int k = 1; k < nlen; ++k) {
+      for (int k = 0; k < nlen; ++k) {
         if (s[cand + k] != needle[k]) { ok = false; break; }
       }
       if (ok) return cand;
@@ -263,13 +283,16 @@ torch::Tensor like_mask(torch::Tensor offsets, torch::Tensor bytes, py::bytes pa
                            torch::TensorOptions().dtype(torch::kUInt8));
   std::memcpy(patT.data_ptr(), pat.data(), pat.size());
   patT = patT.to(offsets.device());
-  // fast path: pure containment '%abc%' (no '_' inside)
-  bool pure_contains = pat.size() >= 2 && pat.front() == '%' && pat.back() == '%' &&
-                       pat.find('_') == std::string::npos &&
-                       pat.find('%', 1) == pat.size() - 1;
-  // '%s1%s2%...%': floating-segment chain (no '_' anywhere)
-  bool chain = !pure_contains && pat.size() >= 2 && pat.front() == '%' &&
-               pat.back() == '%' && pat.find('_') == std::string::npos;
+  // the two scanners below take their needles as plain bytes: a pattern with
+  // '_' or an escape ('\') goes to the generic matcher, which knows both
+  bool plain = pat.find('_') == std::string::npos &&
+               pat.find('\\') == std::string::npos;
+  // fast path: pure containment '%abc%'
+  bool pure_contains = plain && pat.size() >= 2 && pat.front() == '%' &&
+                       pat.back() == '%' && pat.find('%', 1) == pat.size() - 1;
+  // '%s1%s2%...%': floating-segment chain
+  bool chain = !pure_contains && plain && pat.size() >= 2 &&
+               pat.front() == '%' && pat.back() == '%';
   hipStream_t stream = c10::hip::getCurrentHIPStream();
   if (pure_contains) {
     hipLaunchKernelGGL(contains_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream,

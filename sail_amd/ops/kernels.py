@@ -58,11 +58,17 @@ def like_mask(col, pattern: str, case_insensitive=False, is_regex=False) -> Opti
     return ext.like_mask(col.offsets, col.bytes_, pattern.encode())
 
 
+def like_escape(needle: str) -> str:
+    """`needle` as a LIKE pattern that matches exactly its own bytes: the
+    wildcards and the escape byte itself are escaped."""
+    return "".join("\\" + ch if ch in "%_\\" else ch for ch in needle)
+
+
 def string_predicate(col, kind: str, pattern: str) -> Optional[torch.Tensor]:
     if not col.is_cuda:
         return None
     ext = require()
-    pat = pattern.encode()
+    pat = like_escape(pattern).encode()
     if kind == "contains":
         return ext.like_mask(col.offsets, col.bytes_, b"%" + pat + b"%")
     if kind == "startswith":

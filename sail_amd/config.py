@@ -36,6 +36,12 @@ DEFAULTS: Dict[str, str] = {
     # off = pq_bytearray_walk + pq_gather_strings (env
     # SAIL_IO_GPU_BYTEARRAY_FAST, read on every decode)
     "sail.io.gpu_bytearray_fast": "on",
+    # column chunks reach the device through the extension's pipelined reader
+    # (ops/csrc/scan_reader.h, scan_reader.hip): pread into a small ring of
+    # pinned slices, each copied as it completes; off = the Python reader
+    # with one column-sized pinned buffer and one copy (env
+    # SAIL_IO_NATIVE_READER, read on every upload)
+    "sail.io.native_reader": "on",
     # kernels
     "sail.kernels.require_on_gpu": "true",
     "sail.kernels.grouped_agg_max_lds_groups": "4096",

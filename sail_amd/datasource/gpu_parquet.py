@@ -9,6 +9,15 @@ and launches batched page-table kernels (ops/csrc/parquet_decode.hip,
 ops/csrc/parquet_types.hip).
 Decoded columns are born as device tensors — no pyarrow on the hot path.
 
+The chunk bytes of a column reach the device through the extension's
+pipelined reader (ops/csrc/scan_reader.h, scan_reader.hip, pq_read_ranges):
+a persistent pool of workers preads 16 MiB slices into a ring of 8 pinned
+slots and each slice is copied on the copy stream as soon as it is complete,
+so the file read and the copy of one column overlap and the pinned footprint
+stays at the ring. SAIL_IO_NATIVE_READER=off, and every CPU run, takes the
+Python reader instead: a thread pool fills one column-sized pinned buffer,
+then one copy.
+
 Supported: uncompressed v1 and v2 data pages (mixed freely within a
 column), PLAIN fixed-width, PLAIN byte_array, RLE_DICTIONARY (+PLAIN
 dictionary pages), string columns that fall back from RLE_DICTIONARY to
@@ -125,6 +134,16 @@ def bytearray_fast_enabled() -> bool:
     pq_gather_strings. Read on every decode, so one process can alternate
     the two pairs."""
     v = os.environ.get("SAIL_IO_GPU_BYTEARRAY_FAST", "on")
+    return str(v).lower() not in ("off", "false", "0")
+
+
+def native_reader_enabled() -> bool:
+    """SAIL_IO_NATIVE_READER (config sail.io.native_reader), default on: on
+    a GPU the bytes of a column's chunks go through the extension's
+    pipelined reader (pq_read_ranges). `off`, `0` or `false` selects the
+    Python reader with its column-sized pinned buffers. Read on every
+    upload, so one process can alternate the two."""
+    v = os.environ.get("SAIL_IO_NATIVE_READER", "on")
     return str(v).lower() not in ("off", "false", "0")
 
 
@@ -484,6 +503,13 @@ def file_index(path: str) -> FileIndex:
     if idx is None:
         idx = FileIndex(path)
         _INDEX_CACHE[key] = idx
+        # a new or changed file: the native reader must not keep reading
+        # through a descriptor of the file this path used to name
+        from ..ops import kernels
+
+        ext = kernels._ext  # only if already loaded: indexing needs no GPU
+        if ext is not None and hasattr(ext, "pq_reader_invalidate"):
+            ext.pq_reader_invalidate(key[0])
     return idx
 
 
@@ -532,10 +558,59 @@ def _copy_stream(device):
     return _COPY_STREAM
 
 
+def _coalesce(ranges: List[Tuple[int, int]]) -> List[Tuple[int, int]]:
+    """Neighbours in the list that are neighbours in the file as one range,
+    empty ranges dropped: the same bytes in fewer reads."""
+    out: List[Tuple[int, int]] = []
+    for s, e in ranges:
+        if e == s:
+            continue
+        if out and out[-1][1] == s:
+            out[-1] = (out[-1][0], e)
+        else:
+            out.append((s, e))
+    return out
+
+
+def _native_reader(device):
+    """The extension, when uploads to `device` go through its pipelined
+    reader: a GPU device, the switch on, the extension loaded and holding
+    the entry point. None selects the Python reader below."""
+    if not (native_reader_enabled() and str(device).startswith("cuda")
+            and torch.cuda.is_available()):
+        return None
+    from ..ops import kernels
+
+    ext = kernels._load()
+    return ext if hasattr(ext, "pq_read_ranges") else None
+
+
 def _upload_ranges(path: str, ranges: List[Tuple[int, int]], device):
-    """Read file byte ranges into pinned staging, one H2D copy; returns
-    (device u8 tensor, [staging offset per range])."""
+    """File byte ranges -> one device u8 tensor of their concatenation plus
+    16 zero bytes; returns (tensor, [offset per range]). On a GPU the
+    extension's reader streams the bytes through a ring of pinned slices
+    (pq_read_ranges: reads and copies overlap within the column). Otherwise:
+    read into pinned staging, one H2D copy."""
     total = sum(e - s for s, e in ranges)
+    ext = _native_reader(device)
+    if ext is not None:
+        offs = []
+        pos = 0
+        for s, e in ranges:
+            offs.append(pos)
+            pos += e - s
+        # allocated under the copy stream and handed to the compute stream,
+        # as the staged copy below: a block the allocator recycles is never
+        # written while an earlier kernel still reads it
+        cs = _copy_stream(device)
+        cur = torch.cuda.current_stream()
+        with torch.cuda.stream(cs):
+            dev = torch.empty(total + 16, dtype=torch.uint8, device=device)
+            ext.pq_read_ranges(os.path.abspath(path), _coalesce(ranges), dev,
+                               cs.cuda_stream)
+        cur.wait_stream(cs)
+        dev.record_stream(cur)
+        return dev, offs
     slot, stage = _STAGING.acquire(total + 16)  # +16: aligned-word kernels
     view = stage.numpy()                        # may read past the last page
     offs = []

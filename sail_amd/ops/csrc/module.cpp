@@ -59,6 +59,16 @@ torch::Tensor mfma_sum_f64(torch::Tensor x, bool use_mfma);
 torch::Tensor pq_gather_strings(torch::Tensor buf, torch::Tensor src_pos,
                                 torch::Tensor lengths, torch::Tensor out_offsets,
                                 int64_t total_bytes);
+// scan_reader.hip
+int64_t pq_read_ranges(const std::string& path,
+                       const std::vector<std::pair<int64_t, int64_t>>& ranges,
+                       torch::Tensor dst, int64_t copy_stream);
+int64_t pq_reader_read_only(const std::string& path,
+                            const std::vector<std::pair<int64_t, int64_t>>& ranges);
+void pq_reader_configure(int64_t threads, int64_t slice_bytes, int64_t slots);
+std::vector<int64_t> pq_reader_info();
+void pq_reader_invalidate(const std::string& path);
+void pq_reader_shutdown();
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "sail_amd MI355X (gfx950) kernels";
@@ -113,4 +123,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def(
       "pq_gather_bytes", &pq_gather_bytes,
       "gather byte_array payloads, work divided by output bytes");
+  // scan_reader.hip: host half tested by tests/native/scan_reader_check.cpp,
+  // device half by tests/test_native_reader.py
+  m.def(
+      "pq_read_ranges", &pq_read_ranges,
+      "file ranges -> device buffer through a ring of pinned slices; returns "
+      "once every copy is issued on copy_stream",
+      py::arg("path"), py::arg("ranges"), py::arg("dst"), py::arg("copy_stream"));
+  m.def(
+      "pq_reader_read_only", &pq_reader_read_only,
+      "the reader's file read alone, bytes dropped (measurement)",
+      py::arg("path"), py::arg("ranges"));
+  m.def(
+      "pq_reader_configure", &pq_reader_configure,
+      "threads, slice bytes and slots of the reader's ring (0: environment)",
+      py::arg("threads") = 0, py::arg("slice_bytes") = 0, py::arg("slots") = 0);
+  m.def(
+      "pq_reader_info", &pq_reader_info,
+      "(threads, slice bytes, slots, pinned bytes held)");
+  m.def(
+      "pq_reader_invalidate", &pq_reader_invalidate,
+      "forget the cached descriptor of a path");
+  m.def(
+      "pq_reader_shutdown", &pq_reader_shutdown,
+      "join the reader's workers and free its ring");
+  // the workers are joined before the interpreter goes down
+  py::module_::import("atexit").attr("register")(m.attr("pq_reader_shutdown"));
 }

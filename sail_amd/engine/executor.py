@@ -1500,10 +1500,9 @@ class Executor:
 
     def _x_RefreshTable(self, p: S.RefreshTable) -> Chunk:
         # drop cached parquet page indexes + device dictionaries + stats
-        from ..datasource import gpu_parquet as G
+        from ..datasource.pq_index import forget_files
 
-        G._INDEX_CACHE.clear()
-        G._DICT_CACHE.clear()
+        forget_files()
         cat = self.ctx.session.catalog
         k = cat._key(p.name)
         cat._col_stats = {key: v for key, v in cat._col_stats.items()

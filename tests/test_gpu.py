@@ -697,8 +697,7 @@ def test_decode_determinism_stress(tmp_path):
 
     base = snap()
     for _ in range(4):
-        G._INDEX_CACHE.clear()  # force fresh page tables + dict decode
-        G._DICT_CACHE.clear()
+        G.forget_files()  # force fresh page tables + dict decode
         again = snap()
         for k in base:
             assert again[k] == base[k], f"nondeterministic decode: {k}"

@@ -243,7 +243,7 @@ def test_scanned_dicts_are_lex_sorted(tmp_path, sim):
     pq.write_table(pa.table({"s": pa.array(vals2)}), p2,
                    use_dictionary=["s"], compression="none",
                    row_group_size=600)
-    for _ in range(2):  # second pass exercises _DICT_CACHE
+    for _ in range(2):  # second pass reuses the merged dictionary
         out2 = G.read_gpu([p2], [("s", None)], "cpu")
         dv2 = out2.columns["s"].dict_values()
         assert dv2 == sorted(dv2)
@@ -294,3 +294,129 @@ def test_scan_min_max_over_dict_strings(tmp_path, sim):
     rows = s.sql("SELECT k, MIN(s), MAX(s) FROM t GROUP BY k ORDER BY k"
                  ).collect()
     assert rows == [(k, exp[k][0], exp[k][1]) for k in sorted(exp)]
+
+
+# ---------------------------------------------------------------------------
+# who owns what is cached about a file: REFRESH TABLE and replaced files
+# ---------------------------------------------------------------------------
+
+def _write_delta(path, factor=1):
+    vals = np.arange(3000, dtype=np.int64) * factor
+    pq.write_table(pa.table({"k": pa.array(vals)}), path, compression="NONE",
+                   use_dictionary=False,
+                   column_encoding={"k": "DELTA_BINARY_PACKED"})
+    return vals.tolist()
+
+
+def _read_k(path):
+    return G.read_gpu([path], [("k", None)], "cpu").columns["k"].to_pylist()
+
+
+def test_refresh_releases_the_index(tmp_path, sim):
+    """A non-null DELTA column gets its page tables remembered; forgetting
+    the files frees the index and takes its tables out of the byte count."""
+    import gc
+    import weakref
+
+    import sail_amd
+
+    p = str(tmp_path / "delta.parquet")
+    want = _write_delta(p)
+    G.forget_files()
+    session = sail_amd.SessionContext(device="cpu")
+    session.sql(f"CREATE TEMP VIEW refreshed AS SELECT * FROM parquet.`{p}`")
+    for refresh in (G.forget_files,
+                    lambda: session.sql("REFRESH TABLE refreshed").collect()):
+        assert _read_k(p) == want
+        assert G.file_index(p)._tables and G.cached_table_bytes() > 0
+        ref = weakref.ref(G.file_index(p))
+        refresh()
+        gc.collect()
+        assert ref() is None
+        assert G.cached_table_bytes() == 0
+
+
+def test_replaced_file_drops_its_old_index(tmp_path, sim):
+    import gc
+    import weakref
+
+    p = str(tmp_path / "delta.parquet")
+    G.forget_files()
+    want = _write_delta(p)
+    assert _read_k(p) == want
+    ref = weakref.ref(G.file_index(p))
+    held = G.cached_table_bytes()
+    assert held > 0
+    want = _write_delta(p, factor=7)
+    os.utime(p, ns=(1, 1))       # a new generation whatever the clock's grain
+    assert _read_k(p) == want
+    gc.collect()
+    assert ref() is None
+    assert G.cached_table_bytes() == held     # the old tables went with it
+
+
+def test_no_stale_dictionary_after_refresh(tmp_path, sim):
+    """Nullable v1 dictionary pages: nothing of the column is remembered in
+    page tables, so after a refresh only the dictionary values could be
+    stale. A freed index's address is reused by the next one."""
+    import gc
+
+    p = str(tmp_path / "dict.parquet")
+    mask = np.arange(1000) % 5 == 0
+    for factor in range(1, 9):
+        vals = (np.arange(1000, dtype=np.int64) % 4 + 1) * factor
+        t = pa.table({"x": pa.array(vals, mask=mask)})
+        pq.write_table(t, p, compression="NONE", data_page_version="1.0",
+                       use_dictionary=True)
+        got = G.read_gpu([p], [("x", None)], "cpu").columns["x"].to_pylist()
+        assert got == t.column("x").to_pylist(), factor
+        G.forget_files()
+        gc.collect()
+
+
+def test_dictionary_strings_across_refresh(tmp_path, monkeypatch):
+    """Two row groups with different value sets: the merged dictionary is
+    built once per index, reused by the next read, and rebuilt from the
+    new file after a refresh."""
+    import pq_bytearray_sim
+
+    calls = []
+
+    class Counting:
+        def __getattr__(self, name):
+            fn = getattr(pq_bytearray_sim.SIM, name)
+
+            def call(*a):
+                calls.append(name)
+                return fn(*a)
+            return call
+
+    monkeypatch.setattr(G, "_ext", lambda: Counting())
+    monkeypatch.setattr(G, "_ALLOW_CPU", True)
+    monkeypatch.delenv("SAIL_IO_GPU_BYTEARRAY_FAST", raising=False)
+    p = str(tmp_path / "s.parquet")
+
+    def write(words):
+        vals = [words[i % 4] for i in range(700)] + \
+            [words[3 + i % 4] for i in range(700)]
+        pq.write_table(pa.table({"s": pa.array(vals)}), p,
+                       use_dictionary=["s"], compression="none",
+                       row_group_size=700, data_page_version="1.0")
+        assert pq.ParquetFile(p).metadata.num_row_groups == 2
+        return vals
+
+    def read():
+        col = G.read_gpu([p], [("s", None)], "cpu").columns["s"]
+        assert col.is_dict
+        return col.to_pylist(), calls.count("pq_bytearray_index")
+
+    G.forget_files()
+    first = write(["pear", "fig", "apple", "kiwi", "plum", "lime", "date"])
+    got, n1 = read()
+    assert got == first and n1 == 2         # one dictionary page per row group
+    got, n2 = read()
+    assert got == first and n2 == n1        # the merged dictionary is reused
+    G.forget_files()
+    second = write(["delta", "alpha", "golf", "bravo", "echo", "hotel", "cab"])
+    got, n3 = read()
+    assert got == second and n3 == n1 + 2

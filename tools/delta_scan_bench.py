@@ -91,7 +91,7 @@ def _kernel_ab(ext, idx, name, warmup, runs):
     for _ in range(runs):
         t_old.append(_event_ms(old))
         t_new.append(_event_ms(new))
-    packed = int(tabs.rows["delta"][:, 1].sum())
+    packed = int(tabs.rows["delta"][:, G.SRC_LEN].sum())
     w = 4 if i32 else 8
     new_bytes = packed + total * w
     # fill 8N, deltas out 8N, scan in and out 16N, cast in 8N and out 4N
@@ -114,8 +114,7 @@ def _scans(idx, path, name, warmup, runs):
         return G.read_gpu([path], schema, DEV)
 
     def cold_scan():
-        idx._tables.clear()
-        idx._windows.clear()
+        idx.forget()   # the parsed page headers stay: tables are rebuilt
         return scan()
 
     def upload():

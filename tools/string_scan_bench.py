@@ -227,14 +227,11 @@ def _kernels(path, column, warmup, runs, ext):
     dec = G._ColumnDecoder(G.file_index(path), column, DEV, snappy=False)
     dec.upload()
     _, dense_counts = dec.decode_validity()
-    rows, base, pi = [], 0, 0
-    for ch in dec.chunks:
-        for p in ch.pages:
-            if p.enc == G.PLAIN:
-                rows.append((dec._val_off(ch, p), p.val_len, dense_counts[pi],
-                             base, 0, 0))
-                base += dense_counts[pi]
-            pi += 1
+    rows, base = [], 0
+    for p, _, _, off, c, _ in dec._walk(dense_counts):
+        if p.enc == G.PLAIN:
+            rows.append(G.PageRow(off, p.val_len, c, base))
+            base += c
     table = G._page_table(rows, DEV)
     buf = dec.buf
     old_len, old_pos = ext.pq_bytearray_walk(buf, table, base)

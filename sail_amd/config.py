@@ -23,6 +23,11 @@ DEFAULTS: Dict[str, str] = {
     # distributed exchanges (SPMD over RCCL)
     "sail.exec.broadcast_threshold_bytes": str(2 << 30),  # gathered build side above this -> hash shuffle
     "sail.exec.agg_shuffle_threshold_groups": "4000000",  # est. groups above this -> shuffled aggregation
+    # GROUP BY above 4096 groups and direct-address aggregation through
+    # grouped_acc_global (ops/csrc/hash_agg.hip); off = torch index_add_ /
+    # scatter_reduce_, one call per aggregate (env SAIL_EXEC_AGG_GLOBAL, read
+    # on every aggregate)
+    "sail.exec.agg_global": "on",
     # scan path: GPU parquet page decode (datasource/gpu_parquet.py)
     # auto = GPU decode when supported, host pyarrow otherwise;
     # force = raise instead of falling back (tests); off = host only

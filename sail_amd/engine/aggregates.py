@@ -7,6 +7,7 @@ against this module.
 """
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Tuple
 
 import torch
@@ -756,20 +757,51 @@ def global_ids(n: int, device) -> Tuple[torch.Tensor, int]:
 # fused GPU aggregation (ops/csrc/hash_agg.hip)
 # ---------------------------------------------------------------------------
 
+def agg_global_enabled() -> bool:
+    """SAIL_EXEC_AGG_GLOBAL (config sail.exec.agg_global), default on: a
+    GROUP BY above 4096 groups and direct-address aggregation go through
+    grouped_acc_global. `off`, `0` or `false` selects the torch calls. Read on
+    every aggregate, so one process can alternate the two."""
+    v = os.environ.get("SAIL_EXEC_AGG_GLOBAL")
+    return v is None or v.lower() not in ("off", "false", "0")
+
+
+def _global_ext():
+    """The extension when grouped_acc_global may be used, else None."""
+    from ..ops import kernels as K
+
+    if not agg_global_enabled() or not K.available():
+        return None
+    ext = K.require()
+    return ext if hasattr(ext, "grouped_acc_global") else None
+
+
+def _acc_global(ext, gid, mask, vals, ops, ng):
+    """One grouped_acc_global launch. The kernel takes bool masks and every
+    column dtype as stored; it only insists on contiguous memory."""
+    vals = [v if v is None else v.contiguous() for v in vals]
+    mask = mask if mask is None else mask.contiguous()
+    return ext.grouped_acc_global(gid, mask, vals, ops, ng)
+
+
 def fused_agg_batch(aggs, args_list, fmasks, gid: torch.Tensor, ng: int):
-    """Evaluate a whole aggregate list in one (or few) fused kernel passes.
+    """Evaluate a whole aggregate list in one (or few) fused kernel passes:
+    grouped_acc up to 4096 groups, grouped_acc_global above.
 
     aggs: list of S.AggFunc; args_list[i]: evaluated arg Columns;
     fmasks[i]: optional bool mask (FILTER clause). Returns list[Column] or
     None when ineligible (falls back to per-agg torch path).
     """
-    if not gid.is_cuda or ng > 4096 or ng == 0:
+    if not gid.is_cuda or ng == 0:
         return None
     from ..ops import kernels as K
 
     if not K.available():
         return None
     ext = K.require()
+    use_global = ng > 4096
+    if use_global and (ng >= 1 << 31 or _global_ext() is None):
+        return None
 
     n = gid.shape[0]
     # plan columns: per agg -> list of (value_tensor|None, op) + finalizer
@@ -835,7 +867,8 @@ def fused_agg_batch(aggs, args_list, fmasks, gid: torch.Tensor, ng: int):
         vidx = add((data, op))
         plans.append(("minmax", mkey, vidx, (op, c), a))
 
-    gid32 = gid.to(torch.int32)
+    # grouped_acc_global reads int64 ids as they are
+    gid_k = gid.contiguous() if use_global else gid.to(torch.int32)
     results = {}
     for mkey, (fm, cols) in launches.items():
         outs = []
@@ -846,8 +879,11 @@ def fused_agg_batch(aggs, args_list, fmasks, gid: torch.Tensor, ng: int):
             chunk_cols = cols[i : i + 4]
             vals = [t for t, _ in chunk_cols]
             ops = [int(op) for _, op in chunk_cols]
-            mask_t = fm.to(torch.uint8) if fm is not None and fm.dtype == torch.bool else fm
-            out = ext.grouped_acc(gid32, mask_t, vals, ops, ng)
+            if use_global:
+                out = _acc_global(ext, gid_k, fm, vals, ops, ng)
+            else:
+                mask_t = fm.to(torch.uint8) if fm is not None and fm.dtype == torch.bool else fm
+                out = ext.grouped_acc(gid_k, mask_t, vals, ops, ng)
             outs.extend(out[j] for j in range(out.shape[0]))
         results[mkey] = outs
 
@@ -902,13 +938,73 @@ def fused_agg_batch(aggs, args_list, fmasks, gid: torch.Tensor, ng: int):
     return out_cols
 
 
+def _direct_accumulate_torch(packed, prepared, total):
+    """try_direct_aggregate's tables, one index_add_ each. Returns the
+    presence count and per aggregate (table, row count or None)."""
+    dev = packed.device
+
+    def count(mask):
+        idx = packed if mask is None else packed[mask]
+        acc = torch.zeros(total, dtype=torch.int64, device=dev)
+        acc.index_add_(0, idx, torch.ones(idx.shape[0], dtype=torch.int64, device=dev))
+        return acc
+
+    cnt = count(None)
+    accs = []
+    for mask, data, _ in prepared:
+        if data is None:
+            accs.append((cnt if mask is None else count(mask), None))
+            continue
+        acc = torch.zeros(total, dtype=data.dtype, device=dev)
+        if mask is None:
+            acc.index_add_(0, packed, data)
+            accs.append((acc, cnt))
+        else:
+            acc.index_add_(0, packed[mask], data[mask])
+            accs.append((acc, count(mask)))
+    return cnt, accs
+
+
+def _direct_accumulate_fused(ext, packed, prepared, total):
+    """The same tables from grouped_acc_global: one launch group per row
+    mask, up to 4 columns per launch, each group's row count its column 0
+    (for the unmasked group that is the presence count). The mask goes to the
+    kernel, so nothing is compacted."""
+    groups = {0: (None, [(None, 2)])}
+    where = []
+    for mask, data, is_f in prepared:
+        key = 0 if mask is None else id(mask)
+        cols = groups.setdefault(key, (mask, [(None, 2)]))[1]
+        if data is not None:
+            cols.append((data, 1 if is_f else 0))
+        where.append(len(cols) - 1 if data is not None else 0)
+    outs = {}
+    for key, (mask, cols) in groups.items():
+        rows = []
+        for i in range(0, len(cols), 4):
+            chunk = cols[i:i + 4]
+            out = _acc_global(ext, packed, mask, [t for t, _ in chunk],
+                              [op for _, op in chunk], total)
+            rows.extend(out[j] for j in range(out.shape[0]))
+        outs[key] = rows
+    accs = []
+    for (mask, data, is_f), idx in zip(prepared, where):
+        rows = outs[0 if mask is None else id(mask)]
+        if data is None:
+            accs.append((rows[0], None))
+        else:
+            accs.append((rows[idx].view(torch.float64) if is_f else rows[idx], rows[0]))
+    return outs[0][0], accs
+
+
 DIRECT_MIN_ROWS = 1_000_000
 
 
 def try_direct_aggregate(key_cols: List[Column], aggs, args_list, fmasks):
     """Direct-address aggregation for dense high-cardinality keys
     (150M l_orderkey groups in q18): accumulate straight into a span-sized
-    table with index_add and compact once — skips the whole gid machinery
+    table (grouped_acc_global launches of up to 4 columns, or index_add
+    without the kernel) and compact once — skips the whole gid machinery
     (presence bitmap + cumsum + lut gather + representative scatter were 4
     extra random passes over 600M rows). Key VALUES are reconstructed
     arithmetically from the slot index, so no representative gather either.
@@ -917,7 +1013,6 @@ def try_direct_aggregate(key_cols: List[Column], aggs, args_list, fmasks):
     if not key_cols:
         return None
     n = len(key_cols[0])
-    dev = key_cols[0].device
     if n < DIRECT_MIN_ROWS:
         return None
     for c in key_cols:
@@ -946,8 +1041,42 @@ def try_direct_aggregate(key_cols: List[Column], aggs, args_list, fmasks):
     for i in range(1, len(norm)):
         packed = packed * spans[i] + (norm[i] - mins[i])
 
-    cnt = torch.zeros(total, dtype=torch.int64, device=dev)
-    cnt.index_add_(0, packed, torch.ones(n, dtype=torch.int64, device=dev))
+    # per aggregate: its row mask and, for sum / avg, the values to add
+    prepared = []
+    for a, args, fm in zip(aggs, args_list, fmasks):
+        c = args[0] if args else None
+        mask = None
+        if c is not None and c.validity is not None:
+            mask = c.valid_mask()
+        if fm is not None:
+            mask = fm if mask is None else (mask & fm)
+        if a.name in ("count", "count_if"):
+            if a.name == "count_if":
+                m2 = c.data.to(torch.bool)
+                mask = m2 if mask is None else (mask & m2)
+            prepared.append((mask, None, False))
+            continue
+        data = c.data
+        if data.dtype == torch.bool:
+            data = data.to(torch.int64)
+        is_f = data.dtype.is_floating_point
+        if not is_f:
+            amax = int(data.abs().max().item()) if n else 0
+            if amax and amax > (1 << 62) // max(n, 1):
+                data = data.to(torch.float64)
+                is_f = True
+            elif data.dtype != torch.int64:
+                data = data.to(torch.int64)
+        else:
+            data = data.to(torch.float64)
+        prepared.append((mask, data, is_f))
+
+    # the kernel takes G < 2^31; a span of exactly 2^31 stays on index_add_
+    ext = _global_ext() if packed.is_cuda and total < (1 << 31) else None
+    if ext is not None:
+        cnt, accs = _direct_accumulate_fused(ext, packed, prepared, total)
+    else:
+        cnt, accs = _direct_accumulate_torch(packed, prepared, total)
     present = cnt > 0
     out_idx = torch.nonzero(present, as_tuple=False).flatten()
 
@@ -967,49 +1096,12 @@ def try_direct_aggregate(key_cols: List[Column], aggs, args_list, fmasks):
             out_keys.append(Column(c.dtype, code.to(c.data.dtype), None))
 
     agg_cols: List[Column] = []
-    for a, args, fm in zip(aggs, args_list, fmasks):
+    for a, args, (_, data, is_f), (acc, gcnt) in zip(aggs, args_list, prepared, accs):
         name = a.name
         c = args[0] if args else None
-        mask = None
-        if c is not None and c.validity is not None:
-            mask = c.valid_mask()
-        if fm is not None:
-            mask = fm if mask is None else (mask & fm)
-        if name in ("count", "count_if"):
-            if name == "count_if":
-                m2 = c.data.to(torch.bool)
-                mask = m2 if mask is None else (mask & m2)
-            if mask is None:
-                agg_cols.append(Column(T.I64, cnt.index_select(0, out_idx)))
-                continue
-            acc = torch.zeros(total, dtype=torch.int64, device=dev)
-            acc.index_add_(0, packed[mask],
-                           torch.ones(int(mask.sum()), dtype=torch.int64, device=dev))
+        if data is None:
             agg_cols.append(Column(T.I64, acc.index_select(0, out_idx)))
             continue
-        # sum / avg
-        data = c.data
-        if data.dtype == torch.bool:
-            data = data.to(torch.int64)
-        is_f = data.dtype.is_floating_point
-        if not is_f:
-            amax = int(data.abs().max().item()) if n else 0
-            if amax and amax > (1 << 62) // max(n, 1):
-                data = data.to(torch.float64)
-                is_f = True
-            elif data.dtype != torch.int64:
-                data = data.to(torch.int64)
-        else:
-            data = data.to(torch.float64)
-        acc = torch.zeros(total, dtype=data.dtype, device=dev)
-        if mask is None:
-            acc.index_add_(0, packed, data)
-            gcnt = cnt
-        else:
-            acc.index_add_(0, packed[mask], data[mask])
-            gcnt = torch.zeros(total, dtype=torch.int64, device=dev)
-            gcnt.index_add_(0, packed[mask],
-                            torch.ones(int(mask.sum()), dtype=torch.int64, device=dev))
         sums = acc.index_select(0, out_idx)
         if name in ("avg", "try_avg"):
             gc = gcnt.index_select(0, out_idx)

@@ -1,7 +1,8 @@
 // Grouped aggregation kernels for MI355X (gfx950).
 //
 // The hot path of TPC-H Q1-style aggregates: one pass over the value
-// columns, accumulating per group id. Two variants by group count G:
+// columns, accumulating per group id. grouped_acc has two variants by group
+// count G, grouped_acc_global serves every G below 2^31:
 //
 //  * grouped_acc_tiny  (G <= 8): per-thread REGISTER accumulators with
 //    predicated updates (`acc[g] += (gid==g) ? v : 0`, fully unrolled so
@@ -13,11 +14,14 @@
 //    2048 groups x 10 columns, or 4096 groups x 4 columns (128 KB, the
 //    engine's largest launch); wider launches above 2048 groups are refused.
 //
-// Larger G falls back to torch index_add_ (scattered global atomics are
-// fine once contention is low).
+//  * grouped_acc_global (1 <= G < 2^31, int32 or int64 gid): accumulators
+//    in global memory, still one pass for all columns. Runs of equal gid in
+//    a wave are reduced over shuffles to one atomic per run, and a small
+//    claim-once LDS table per workgroup absorbs hot groups scattered through
+//    the input before they serialise on one L2 address.
 //
 // Column ops: 0 = sum i64, 1 = sum f64, 2 = count (value ptr may be null),
-//             3 = min i64, 4 = max i64 (lds variant only).
+//             3 = min i64, 4 = max i64 (lds and global variants).
 // All accumulators are 64-bit; i64 sums use two's-complement atomicAdd.
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -222,6 +226,181 @@ __global__ void grouped_acc_lds(const int32_t* __restrict__ gid,
   }
 }
 
+// ---------------------------------------------------------------------
+// global variant: any G < 2^31, accumulators in `out` itself
+// ---------------------------------------------------------------------
+struct ColPack {
+  ColArg c[10];
+};
+
+// slots of the per-workgroup hot-group cache: 4 B tag + NC * 8 B per slot.
+// 1024 slots x 4 columns = 36 KB, four workgroups per CU's 160 KB; wider
+// launches halve the table (10 columns: 42 KB, three workgroups)
+template <int NC>
+struct GlobalCache {
+  static constexpr int kSlots = NC <= 4 ? 1024 : 512;
+};
+
+constexpr int kGlobalTilesMin = 16;   // rows per workgroup >= 16 * kBlock
+constexpr int kGlobalGridMax = 2048;
+
+__device__ inline long long acc_identity(int op) {
+  return op == 3 ? INT64_MAX : op == 4 ? INT64_MIN : 0;
+}
+
+__device__ inline long long acc_combine(int op, long long a, long long b) {
+  switch (op) {
+    case 1: return __double_as_longlong(__longlong_as_double(a) + __longlong_as_double(b));
+    case 3: return b < a ? b : a;
+    case 4: return b > a ? b : a;
+    default: return (long long)((unsigned long long)a + (unsigned long long)b);
+  }
+}
+
+// one 64-bit update of a cell in LDS or global memory; an update that cannot
+// change the cell (zero bits under a sum, the sentinel under min/max) is
+// skipped when `skip_identity`, as the flush of grouped_acc_lds does
+template <typename Cell>
+__device__ inline void acc_atomic(Cell* cell, int op, long long v, bool skip_identity) {
+  if (skip_identity && v == acc_identity(op)) return;
+  switch (op) {
+    case 1:
+      atomicAdd((double*)cell, __longlong_as_double(v));
+      break;
+    case 3:
+      atomicMin((long long*)cell, v);
+      break;
+    case 4:
+      atomicMax((long long*)cell, v);
+      break;
+    default:
+      atomicAdd((unsigned long long*)cell, (unsigned long long)v);
+      break;
+  }
+}
+
+// One pass over the rows for all NC columns. A workgroup owns a contiguous
+// chunk of rows and walks it in tiles of kBlock; lane i of a wave holds row
+// base + i, so gid, mask and every value column are read coalesced, once.
+//  RUNS:  adjacent live lanes with equal gid form a run; a segmented wave
+//         reduction leaves the run's total in its first lane and only that
+//         lane updates memory. A masked-out or out-of-range row is dead: it
+//         carries the identity and the live lane after it starts a new run.
+//  CACHE: a direct-mapped LDS table (slot = low bits of gid) claimed once by
+//         atomicCAS on the tag, never evicted. The claimant's updates stay
+//         in LDS until the workgroup's flush; every other gid of that slot
+//         goes to global memory.
+template <typename GidT, int NC, bool RUNS, bool CACHE>
+__global__ __launch_bounds__(kBlock) void grouped_acc_global_kernel(
+    const GidT* __restrict__ gid, const uint8_t* __restrict__ mask, int64_t n,
+    int64_t rows_per_block, ColPack cols, int64_t* __restrict__ out /* [G][NC] */,
+    int G) {
+  constexpr int kSlots = GlobalCache<NC>::kSlots;
+  constexpr int kEmpty = -1;
+  __shared__ int tags[CACHE ? kSlots : 1];
+  __shared__ long long cache[CACHE ? NC : 1][CACHE ? kSlots : 1];
+  if constexpr (CACHE) {
+    for (int s = threadIdx.x; s < kSlots; s += kBlock) {
+      tags[s] = kEmpty;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) cache[c][s] = acc_identity(cols.c[c].op);
+    }
+    __syncthreads();
+  }
+
+  const int lane = threadIdx.x & 63;
+  const int64_t begin = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t end = begin + rows_per_block < n ? begin + rows_per_block : n;
+  for (int64_t base = begin; base < end; base += kBlock) {
+    const int64_t i = base + threadIdx.x;
+    bool live = i < end;
+    int g = 0;
+    if (live) {
+      GidT raw = gid[i];
+      live = raw >= 0 && raw < (GidT)G && (!mask || mask[i]);
+      g = (int)raw;
+    }
+    long long v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const ColArg a = cols.c[c];
+      v[c] = acc_identity(a.op);
+      if (live) {
+        if (a.op == 2) v[c] = 1;
+        else if (a.op == 1) v[c] = __double_as_longlong(load_as_f64(a.ptr, a.elem, i));
+        else v[c] = load_as_i64(a.ptr, a.elem, i);
+      }
+    }
+
+    bool issue = live;
+    if constexpr (RUNS) {
+      const int gprev = __shfl_up(g, 1, 64);
+      const int lprev = __shfl_up((int)live, 1, 64);
+      const bool head = live && (lane == 0 || !lprev || gprev != g);
+      const unsigned long long heads = __ballot(head);
+      if (heads != __ballot(live)) {
+        // heads among lanes lane+1 .. 63; lane + off joins this lane's run
+        // when no head lies in (lane, lane + off]
+        const unsigned long long after = (heads >> lane) >> 1;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const bool join = lane + off < 64 && (after & ((1ull << off) - 1)) == 0;
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            const long long o = __shfl_down(v[c], off, 64);
+            if (join) v[c] = acc_combine(cols.c[c].op, v[c], o);
+          }
+        }
+      }
+      issue = head;
+    }
+
+    if (issue) {
+      bool cached = false;
+      int slot = 0;
+      if constexpr (CACHE) {
+        slot = g & (kSlots - 1);
+        const int owner = atomicCAS(&tags[slot], kEmpty, g);
+        cached = owner == kEmpty || owner == g;
+      }
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int op = cols.c[c].op;
+        if (CACHE && cached) acc_atomic(&cache[c][slot], op, v[c], false);
+        else acc_atomic(&out[(int64_t)g * NC + c], op, v[c], false);
+      }
+    }
+  }
+
+  if constexpr (CACHE) {
+    __syncthreads();
+    for (int s = threadIdx.x; s < kSlots; s += kBlock) {
+      const int g = tags[s];
+      if (g == kEmpty) continue;
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        acc_atomic(&out[(int64_t)g * NC + c], cols.c[c].op, cache[c][s], true);
+    }
+  }
+}
+
+template <typename GidT, bool RUNS, bool CACHE>
+void launch_global(int ncols, int grid, hipStream_t stream, const void* gid,
+                   const uint8_t* mask, int64_t n, int64_t rows_per_block,
+                   const ColPack& cols, int64_t* out, int G) {
+#define GLOBAL_CASE(NCV)                                                          \
+  case NCV:                                                                       \
+    hipLaunchKernelGGL((grouped_acc_global_kernel<GidT, NCV, RUNS, CACHE>),       \
+                       dim3(grid), dim3(kBlock), 0, stream, (const GidT*)gid,     \
+                       mask, n, rows_per_block, cols, out, G);                    \
+    break;
+  switch (ncols) {
+    GLOBAL_CASE(1) GLOBAL_CASE(2) GLOBAL_CASE(3) GLOBAL_CASE(4) GLOBAL_CASE(5)
+    GLOBAL_CASE(6) GLOBAL_CASE(7) GLOBAL_CASE(8) GLOBAL_CASE(9) GLOBAL_CASE(10)
+  }
+#undef GLOBAL_CASE
+}
+
 ColArg make_col(const c10::optional<torch::Tensor>& t, int op, int64_t n) {
   ColArg a;
   a.op = op;
@@ -338,4 +517,62 @@ torch::Tensor grouped_acc(torch::Tensor gid, c10::optional<torch::Tensor> mask,
                      ncols, out.data_ptr<int64_t>(), (int)G);
   check_launch("grouped_acc_lds");
   return out;
+}
+
+// grouped_acc's contract for any 1 <= G < 2^31 and any op mix: gid is int32
+// or int64, a row whose gid lies outside [0, G) is dropped, and nothing is
+// written outside `out`. variant 0 is the kernel as shipped; 1 switches the
+// run combining off and 2 the LDS cache (tools/agg_global_bench.py).
+torch::Tensor grouped_acc_global(torch::Tensor gid, c10::optional<torch::Tensor> mask,
+                                 std::vector<c10::optional<torch::Tensor>> vals,
+                                 std::vector<int64_t> ops, int64_t G, int64_t variant) {
+  TORCH_CHECK(gid.is_cuda() && gid.is_contiguous() &&
+                  (gid.scalar_type() == torch::kInt32 || gid.scalar_type() == torch::kInt64),
+              "grouped_acc_global: gid must be a contiguous cuda int32 or int64 tensor");
+  int64_t n = gid.numel();
+  int ncols = (int)vals.size();
+  TORCH_CHECK(ncols >= 1 && ncols <= 10, "1..10 columns per launch");
+  TORCH_CHECK((int)ops.size() == ncols, "grouped_acc_global: one op per column");
+  TORCH_CHECK(G >= 1 && G < (int64_t(1) << 31), "grouped_acc_global: G must be in [1, 2^31)");
+  TORCH_CHECK(variant >= 0 && variant <= 2, "grouped_acc_global: variant is 0, 1 or 2");
+  ColPack cols;
+  for (int c = 0; c < 10; ++c)
+    cols.c[c] = make_col(c < ncols ? vals[c] : c10::nullopt, c < ncols ? (int)ops[c] : 2, n);
+  const uint8_t* mptr = nullptr;
+  if (mask.has_value() && mask->defined()) {
+    TORCH_CHECK(mask->scalar_type() == torch::kBool || mask->scalar_type() == torch::kUInt8);
+    TORCH_CHECK(mask->is_cuda() && mask->is_contiguous() && mask->numel() == n,
+                "grouped_acc_global: mask must be a contiguous cuda tensor of gid's length");
+    mptr = (const uint8_t*)mask->data_ptr();
+  }
+  // the kernel accumulates into [G][ncols]: the cells of one group share a
+  // cache line, so a row with a cold gid costs one line of atomic traffic,
+  // not one per column. The result is transposed once at the end.
+  auto acc = torch::zeros({G, ncols}, gid.options().dtype(torch::kInt64));
+  for (int c = 0; c < ncols; ++c) {
+    if (ops[c] == 3) acc.select(1, c).fill_(INT64_MAX);
+    if (ops[c] == 4) acc.select(1, c).fill_(INT64_MIN);
+  }
+  if (n == 0) return acc.t().contiguous();
+  // contiguous chunks of whole tiles, at least kGlobalTilesMin per workgroup
+  // so that a flush of the cache is paid once per few thousand rows
+  int64_t tiles = (n + kBlock - 1) / kBlock;
+  int64_t grid = std::min<int64_t>((tiles + kGlobalTilesMin - 1) / kGlobalTilesMin,
+                                   kGlobalGridMax);
+  int64_t rows_per_block = (tiles + grid - 1) / grid * kBlock;
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  bool wide = gid.scalar_type() == torch::kInt64;
+#define GLOBAL_LAUNCH(RUNS, CACHE)                                                      \
+  (wide ? launch_global<int64_t, RUNS, CACHE>(ncols, (int)grid, stream, gid.data_ptr(), \
+                                              mptr, n, rows_per_block, cols,            \
+                                              acc.data_ptr<int64_t>(), (int)G)          \
+        : launch_global<int32_t, RUNS, CACHE>(ncols, (int)grid, stream, gid.data_ptr(), \
+                                              mptr, n, rows_per_block, cols,            \
+                                              acc.data_ptr<int64_t>(), (int)G))
+  if (variant == 0) GLOBAL_LAUNCH(true, true);
+  else if (variant == 1) GLOBAL_LAUNCH(false, true);
+  else GLOBAL_LAUNCH(true, false);
+#undef GLOBAL_LAUNCH
+  check_launch("grouped_acc_global");
+  return acc.t().contiguous();
 }

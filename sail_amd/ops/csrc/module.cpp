@@ -15,6 +15,9 @@ torch::Tensor str_pairs_equal(torch::Tensor offs_a, torch::Tensor bytes_a,
 torch::Tensor grouped_acc(torch::Tensor gid, c10::optional<torch::Tensor> mask,
                           std::vector<c10::optional<torch::Tensor>> vals,
                           std::vector<int64_t> ops, int64_t G);
+torch::Tensor grouped_acc_global(torch::Tensor gid, c10::optional<torch::Tensor> mask,
+                                 std::vector<c10::optional<torch::Tensor>> vals,
+                                 std::vector<int64_t> ops, int64_t G, int64_t variant);
 // hash_join.hip
 std::vector<torch::Tensor> hj_build(torch::Tensor keys);
 torch::Tensor hj_probe_unique(torch::Tensor tkeys, torch::Tensor tvals, torch::Tensor keys);
@@ -81,6 +84,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "byte-exact equality of (row_a, row_b) string pairs");
   m.def("grouped_acc", &grouped_acc,
         "fused grouped accumulation (sum/count/min/max) for small group counts");
+  m.def(
+      "grouped_acc_global", &grouped_acc_global,
+      "fused grouped accumulation into global memory, 1 <= G < 2^31, int32 or "
+      "int64 gid; variant 1 / 2 switch run combining / the LDS cache off",
+      py::arg("gid"), py::arg("mask"), py::arg("vals"), py::arg("ops"), py::arg("G"),
+      py::arg("variant") = 0);
   m.def("hj_build", &hj_build, "hash join build (unique keys)");
   m.def("hj_probe_unique", &hj_probe_unique, "hash join probe, first match");
   m.def("hj_build_chain", &hj_build_chain, "hash join build with chains");

@@ -41,6 +41,11 @@ DEFAULTS: Dict[str, str] = {
     # off = pq_bytearray_walk + pq_gather_strings (env
     # SAIL_IO_GPU_BYTEARRAY_FAST, read on every decode)
     "sail.io.gpu_bytearray_fast": "on",
+    # DELTA_BYTE_ARRAY (front-coded) string columns decode on the device with
+    # pq_dba_lengths + pq_dba_expand (ops/csrc/parquet_delta_bytearray.hip);
+    # off = the encoding is refused and the file goes to the host path (env
+    # SAIL_IO_GPU_DELTA_BYTEARRAY, read on every decode)
+    "sail.io.gpu_delta_bytearray": "on",
     # column chunks reach the device through the extension's pipelined reader
     # (ops/csrc/scan_reader.h, scan_reader.hip): pread into a small ring of
     # pinned slices, each copied as it completes; off = the Python reader

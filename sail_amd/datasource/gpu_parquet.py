@@ -13,13 +13,23 @@ Supported: uncompressed v1 and v2 data pages (mixed freely within a
 column), PLAIN fixed-width, PLAIN byte_array, RLE_DICTIONARY (+PLAIN
 dictionary pages), string columns that fall back from RLE_DICTIONARY to
 PLAIN pages, DELTA_BINARY_PACKED, DELTA_LENGTH_BYTE_ARRAY,
-BYTE_STREAM_SPLIT on INT32/INT64/FLOAT/DOUBLE, BOOLEAN (PLAIN and RLE),
+DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT on INT32/INT64/FLOAT/DOUBLE, BOOLEAN (PLAIN and RLE),
 INT96 timestamps (PLAIN and dictionary; decoded to int64 microseconds),
 FLBA/INT32/INT64 decimals, definition levels (nulls). Anything else raises
 Unsupported and the caller falls back to the host pyarrow path
 (parquet_io.read): v2 pages in a compressed chunk, codecs other than
-opt-in Snappy, DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT on FIXED_LEN_BYTE_ARRAY,
+opt-in Snappy, DELTA_BYTE_ARRAY on FIXED_LEN_BYTE_ARRAY or mixed with another
+encoding in one column, BYTE_STREAM_SPLIT on FIXED_LEN_BYTE_ARRAY,
 dictionary-encoded BOOLEAN, nested columns.
+
+DELTA_BYTE_ARRAY (front-coded) string pages decode in two launches
+(ops/csrc/parquet_delta_bytearray.hip): pq_dba_lengths reads both length
+streams of every page and checks all the format asks of them, their running
+sum gives the output offsets, and pq_dba_expand rebuilds the values, one
+wave per page, in an LDS buffer it edits in place. A page either kernel
+rejects raises Unsupported. SAIL_IO_GPU_DELTA_BYTEARRAY=off refuses the
+encoding. A chunk that mixes it with dictionary pages (parquet-java's v2
+dictionary fallback) is still refused.
 
 DELTA_BINARY_PACKED integer pages decode with one launch of pq_delta_values
 (ops/csrc/parquet_delta.hip), which writes final values of the column's own
@@ -72,11 +82,12 @@ from ..engine.column import Column, StringColumn, Table
 # re-exported: callers and tests reach the index, the switches and the
 # upload through this module
 from .pq_index import (  # noqa: F401
-    BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED, DELTA_LENGTH_BYTE_ARRAY, PLAIN,
-    PLAIN_DICTIONARY, RLE, RLE_DICTIONARY, TABLE_CACHE_CAP, _INDEX_CACHE,
-    FileIndex, Unsupported, _check_all_valid, bytearray_fast_enabled,
-    cached_table_bytes, delta_fused_enabled, file_index, forget_files,
-    native_reader_enabled, snappy_enabled)
+    BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED, DELTA_BYTE_ARRAY,
+    DELTA_LENGTH_BYTE_ARRAY, PLAIN, PLAIN_DICTIONARY, RLE, RLE_DICTIONARY,
+    TABLE_CACHE_CAP, _INDEX_CACHE, FileIndex, Unsupported, _check_all_valid,
+    bytearray_fast_enabled, cached_table_bytes, delta_bytearray_enabled,
+    delta_fused_enabled, file_index, forget_files, native_reader_enabled,
+    snappy_enabled)
 from .pq_upload import _coalesce, _native_reader, _upload_ranges  # noqa: F401
 
 _JULIAN_UNIX_EPOCH = 2440588          # Julian day number of 1970-01-01
@@ -302,6 +313,13 @@ class _ColumnDecoder:
                   DELTA_LENGTH_BYTE_ARRAY}
             if self.physical in _PHYS_WIDTH:
                 ok.add(BYTE_STREAM_SPLIT)
+            # front-coded strings: with the switch on, and only from an
+            # extension that has the decoder (the kernel simulators of the
+            # tests do not), as for pq_bytearray_index below
+            if self.physical == "BYTE_ARRAY" and DELTA_BYTE_ARRAY in encs \
+                    and delta_bytearray_enabled() \
+                    and hasattr(_ext(), "pq_dba_expand"):
+                ok.add(DELTA_BYTE_ARRAY)
         bad = encs - ok
         if bad:
             raise Unsupported(f"{self.sc.name}: encodings {bad}")
@@ -806,6 +824,30 @@ class _ColumnDecoder:
             lengths = _segmented_cumsum(deltas, dense_counts)
             offsets = torch.zeros(n_dense + 1, dtype=torch.int64, device=dev)
             torch.cumsum(lengths, 0, out=offsets[1:])
+            return self._assemble_strings(offsets, blob, lengths, validity)
+
+        if enc == DELTA_BYTE_ARRAY:
+            # front-coded values: both length streams -> lengths; their
+            # running sum -> output offsets; then one wave per page rebuilds
+            # the values in LDS and writes them (parquet_delta_bytearray.hip)
+            table = _page_table(rows, dev)
+            prefix, suffix, lengths, suffix_start, status = \
+                ext.pq_dba_lengths(self.buf, table, n_dense)
+            offsets = torch.zeros(n_dense + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(lengths, 0, out=offsets[1:])
+            # the one device->host read: the byte total and the rejections
+            total, nbad = torch.stack(
+                [offsets[-1], (status != 0).sum()]).tolist()
+            if nbad:
+                i = int(torch.nonzero(status).flatten()[0].item())
+                raise Unsupported(
+                    f"{self.sc.name}: DELTA_BYTE_ARRAY page {i} of "
+                    f"{len(rows)} rejected, status {int(status[i].item())}")
+            # every rule of the format is settled by now: pq_dba_expand
+            # repeats the checks only to stay in bounds whatever it is handed
+            blob = torch.empty(total, dtype=torch.uint8, device=dev)
+            ext.pq_dba_expand(self.buf, table, prefix, suffix, suffix_start,
+                              offsets, lengths, status, blob)
             return self._assemble_strings(offsets, blob, lengths, validity)
 
         # PLAIN byte arrays: sequential walk + parallel gather

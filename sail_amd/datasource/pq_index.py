@@ -33,6 +33,7 @@ PLAIN_DICTIONARY = 2
 RLE = 3
 DELTA_BINARY_PACKED = 5
 DELTA_LENGTH_BYTE_ARRAY = 6
+DELTA_BYTE_ARRAY = 7
 RLE_DICTIONARY = 8
 BYTE_STREAM_SPLIT = 9
 
@@ -77,6 +78,15 @@ def bytearray_fast_enabled() -> bool:
     pq_gather_strings. Read on every decode, so one process can alternate
     the two pairs."""
     return _switch("SAIL_IO_GPU_BYTEARRAY_FAST", True)
+
+
+def delta_bytearray_enabled() -> bool:
+    """SAIL_IO_GPU_DELTA_BYTEARRAY (config sail.io.gpu_delta_bytearray),
+    default on: DELTA_BYTE_ARRAY string columns decode on the device with
+    pq_dba_lengths + pq_dba_expand. `off`, `0` or `false` refuses the
+    encoding, so such a column goes to the host path. Read on every decode,
+    so one process can alternate the two."""
+    return _switch("SAIL_IO_GPU_DELTA_BYTEARRAY", True)
 
 
 def native_reader_enabled() -> bool:

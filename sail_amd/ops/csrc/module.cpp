@@ -57,6 +57,13 @@ std::vector<torch::Tensor> pq_bytearray_index(torch::Tensor buf, torch::Tensor p
 torch::Tensor pq_gather_bytes(torch::Tensor buf, torch::Tensor src_pos,
                               torch::Tensor lengths, torch::Tensor out_offsets,
                               int64_t total_bytes);
+// parquet_delta_bytearray.hip
+std::vector<torch::Tensor> pq_dba_lengths(torch::Tensor buf, torch::Tensor pages,
+                                          int64_t total);
+void pq_dba_expand(torch::Tensor buf, torch::Tensor pages, torch::Tensor prefix,
+                   torch::Tensor suffix, torch::Tensor suffix_start,
+                   torch::Tensor offsets, torch::Tensor lengths, torch::Tensor status,
+                   torch::Tensor out);
 // mfma_reduce.hip
 torch::Tensor mfma_sum_f64(torch::Tensor x, bool use_mfma);
 torch::Tensor pq_gather_strings(torch::Tensor buf, torch::Tensor src_pos,
@@ -132,6 +139,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def(
       "pq_gather_bytes", &pq_gather_bytes,
       "gather byte_array payloads, work divided by output bytes");
+  // parquet_delta_bytearray.hip: case table in tests/test_pq_dba_kernel.py
+  m.def(
+      "pq_dba_lengths", &pq_dba_lengths,
+      "parquet DELTA_BYTE_ARRAY length streams -> prefix and suffix lengths, "
+      "value lengths, start of the suffix bytes and status per page",
+      py::arg("buf"), py::arg("pages"), py::arg("total"));
+  m.def(
+      "pq_dba_expand", &pq_dba_expand,
+      "parquet DELTA_BYTE_ARRAY front-coded values -> bytes at offsets, in place "
+      "in `out`; updates `status` and zeroes the `lengths` rows of a rejected page",
+      py::arg("buf"), py::arg("pages"), py::arg("prefix"), py::arg("suffix"),
+      py::arg("suffix_start"), py::arg("offsets"), py::arg("lengths"),
+      py::arg("status"), py::arg("out"));
   // scan_reader.hip: host half tested by tests/native/scan_reader_check.cpp,
   // device half by tests/test_native_reader.py
   m.def(

@@ -25,8 +25,8 @@
 // look the same to them (the host finds the regions). SNAPPY v1 pages are
 // expanded first by snappy.hip when sail.io.gpu_snappy is on. Still on the
 // host fallback (datasource/parquet_io.py): v2 pages in a compressed chunk,
-// other codecs, DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT on FIXED_LEN_BYTE_ARRAY,
-// nested columns.
+// other codecs, BYTE_STREAM_SPLIT on FIXED_LEN_BYTE_ARRAY, nested columns.
+// DELTA_BYTE_ARRAY strings are in parquet_delta_bytearray.hip.
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>

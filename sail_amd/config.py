@@ -28,6 +28,11 @@ DEFAULTS: Dict[str, str] = {
     # scatter_reduce_, one call per aggregate (env SAIL_EXEC_AGG_GLOBAL, read
     # on every aggregate)
     "sail.exec.agg_global": "on",
+    # raw string columns on the device are sorted, ranked (ORDER BY, top-k,
+    # MIN/MAX) and compared (<, <=, >, >=) by ops/csrc/string_sort.hip; off =
+    # the host code, one Python object per row (env SAIL_EXEC_STRING_SORT,
+    # read at each use)
+    "sail.exec.string_sort": "on",
     # scan path: GPU parquet page decode (datasource/gpu_parquet.py)
     # auto = GPU decode when supported, host pyarrow otherwise;
     # force = raise instead of falling back (tests); off = host only

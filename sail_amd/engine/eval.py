@@ -565,6 +565,37 @@ def _literal_string_keys(col: StringColumn, lits) -> torch.Tensor:
     return literal_keys_like(list(lits), force_hash, col.device)
 
 
+def _device_string_order(a: StringColumn, b: StringColumn, op: str) -> Optional[torch.Tensor]:
+    """`a op b` for an ordering operator through str_compare3
+    (ops/csrc/string_sort.hip): raw `a` on the device against a raw `b` of the
+    same length, or against one value (a one-row raw column, or a one-entry
+    dictionary, as a broadcast literal arrives). None where that does not
+    apply. Rows with a null on either side give False, as the host loop does.
+    A raw one-row `b` against a longer `a` is broadcast here; the host loop
+    never served that shape (its zip stops after one row), and the evaluator
+    broadcasts its operands before it compares, so no query reaches it."""
+    from ..ops import kernels as K
+
+    n = len(a)
+    if len(b) not in (1, n) or (b.is_dict and b.dict_size != 1):
+        return None  # a dictionary's buffers are its entries, not its rows
+    ext = K.string_sort_ext()
+    if ext is None:
+        return None
+    b = b.to(a.device)
+    c = ext.str_compare3(a.offsets.contiguous(), a.bytes_.contiguous(),
+                         b.offsets.contiguous(), b.bytes_.contiguous())
+    m = {"<": c < 0, "<=": c <= 0, ">": c > 0, ">=": c >= 0}[op]
+    if a.validity is not None:
+        m &= a.valid_mask()
+    bv = b.valid_mask()
+    if b.is_dict:
+        bv = bv & (b.codes >= 0)
+    if b.validity is not None or b.is_dict:
+        m &= bv  # len(b) == 1 broadcasts
+    return m
+
+
 def _string_cmp(a: Column, b: Column, op: str) -> torch.Tensor:
     # dict-encoded vs scalar-dict single-value fast path
     if isinstance(a, StringColumn) and isinstance(b, StringColumn):
@@ -621,6 +652,10 @@ def _string_cmp(a: Column, b: Column, op: str) -> torch.Tensor:
                        ">": keys > target, ">=": keys >= target}[op]
                 lut = torch.from_numpy(cmp).to(a.device)
                 return lut[a.codes.long()]
+        if op in ("<", "<=", ">", ">=") and not a.is_dict and a.is_cuda:
+            m = _device_string_order(a, b, op)
+            if m is not None:
+                return m
         # generic: host comparison (CPU reference path)
         av = a.to_pylist()
         bv = b.to_pylist()

@@ -16,6 +16,7 @@ from typing import Dict, List, Optional
 
 import torch
 
+from ..ops import kernels as K
 from ..plan import spec as S
 from . import types as T
 from .aggregates import agg_eval, global_ids, group_ids
@@ -1627,12 +1628,32 @@ def sort_indices(ev: Evaluator, keys: List[S.SortKey], chunk: Chunk) -> torch.Te
     return idx
 
 
+def string_ranks(col: StringColumn, ext=None) -> torch.Tensor:
+    """Dense ranks of a raw string column in byte order, computed on the
+    device (ops/csrc/string_sort.hip): equal values share a rank, and null
+    rows all get the rank past the last distinct value."""
+    ext = ext or K.require()
+    n = len(col)
+    offsets, bytes_ = col.offsets.contiguous(), col.bytes_.contiguous()
+    rows = None
+    if col.validity is not None:
+        rows = torch.nonzero(col.valid_mask(), as_tuple=False).squeeze(1)
+    perm = ext.str_sort_perm(offsets, bytes_, rows)
+    rank_sorted, ndistinct = ext.str_dense_rank(offsets, bytes_, perm)
+    ranks = ndistinct.expand(n).clone()
+    ranks[perm] = rank_sorted
+    return ranks
+
+
 def _sortable(col: Column) -> torch.Tensor:
     if isinstance(col, StringColumn):
         from .joins import normalize_key
 
         if col.is_dict:
             return col.codes.to(torch.int64)  # dict is sorted => codes ordered
+        ext = K.string_sort_ext() if col.is_cuda else None
+        if ext is not None:
+            return string_ranks(col, ext)
         # raw strings: host DENSE rank (equal values must get equal ranks or
         # stable multi-key sorting breaks on the later keys)
         vals = col.to_pylist()

@@ -11,6 +11,13 @@ torch::Tensor string_hash64_seeded(torch::Tensor offsets, torch::Tensor bytes,
 torch::Tensor str_pairs_equal(torch::Tensor offs_a, torch::Tensor bytes_a,
                               torch::Tensor ia, torch::Tensor offs_b,
                               torch::Tensor bytes_b, torch::Tensor ib);
+// string_sort.hip
+torch::Tensor str_sort_perm(torch::Tensor offsets, torch::Tensor bytes,
+                            c10::optional<torch::Tensor> rows);
+std::vector<torch::Tensor> str_dense_rank(torch::Tensor offsets, torch::Tensor bytes,
+                                          torch::Tensor perm);
+torch::Tensor str_compare3(torch::Tensor offs_a, torch::Tensor bytes_a,
+                           torch::Tensor offs_b, torch::Tensor bytes_b);
 // hash_agg.hip
 torch::Tensor grouped_acc(torch::Tensor gid, c10::optional<torch::Tensor> mask,
                           std::vector<c10::optional<torch::Tensor>> vals,
@@ -89,6 +96,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "seeded 64-bit string hash (second family for exact codes)");
   m.def("str_pairs_equal", &str_pairs_equal,
         "byte-exact equality of (row_a, row_b) string pairs");
+  // string_sort.hip: cases in tests/test_string_sort.py
+  m.def(
+      "str_sort_perm", &str_sort_perm,
+      "stable argsort of raw strings (all rows, or the rows given) in unsigned "
+      "byte order, a prefix first -> int64 row ids",
+      py::arg("offsets"), py::arg("bytes"), py::arg("rows") = py::none());
+  m.def(
+      "str_dense_rank", &str_dense_rank,
+      "dense ranks along a sorted permutation -> (rank per sorted position, "
+      "number of distinct values as int64[1])",
+      py::arg("offsets"), py::arg("bytes"), py::arg("perm"));
+  m.def(
+      "str_compare3", &str_compare3,
+      "row-wise -1/0/1 of two raw string columns; b has as many rows as a, or one",
+      py::arg("offs_a"), py::arg("bytes_a"), py::arg("offs_b"), py::arg("bytes_b"));
   m.def("grouped_acc", &grouped_acc,
         "fused grouped accumulation (sum/count/min/max) for small group counts");
   m.def(

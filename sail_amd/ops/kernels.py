@@ -47,6 +47,23 @@ def require():
     return ext
 
 
+def string_sort_enabled() -> bool:
+    """SAIL_EXEC_STRING_SORT (config sail.exec.string_sort), default on: raw
+    string columns on the device are sorted, ranked and compared by
+    ops/csrc/string_sort.hip. `off`, `0` or `false` selects the host code.
+    Read at each use, so one process can alternate the two."""
+    v = os.environ.get("SAIL_EXEC_STRING_SORT")
+    return v is None or v.lower() not in ("off", "false", "0")
+
+
+def string_sort_ext():
+    """The extension when the string ordering kernels may be used, else None."""
+    if not string_sort_enabled() or not available():
+        return None
+    ext = require()
+    return ext if hasattr(ext, "str_sort_perm") and hasattr(ext, "str_compare3") else None
+
+
 def like_mask(col, pattern: str, case_insensitive=False, is_regex=False) -> Optional[torch.Tensor]:
     """Device LIKE over raw (offsets,bytes) strings. None => no kernel path
     (caller falls back on CPU; on CUDA require())."""

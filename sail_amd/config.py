@@ -28,6 +28,12 @@ DEFAULTS: Dict[str, str] = {
     # scatter_reduce_, one call per aggregate (env SAIL_EXEC_AGG_GLOBAL, read
     # on every aggregate)
     "sail.exec.agg_global": "on",
+    # device equi-joins look each probe row up once (hj_probe_heads /
+    # hj_probe_exists, ops/csrc/hash_join.hip): unique builds and
+    # existence-only joins skip the count/scan/fill passes; off = chain build
+    # + hj_probe_count + hj_probe_fill (env SAIL_EXEC_JOIN_FUSED, read on
+    # every join)
+    "sail.exec.join_fused": "on",
     # raw string columns on the device are sorted, ranked (ORDER BY, top-k,
     # MIN/MAX) and compared (<, <=, >, >=) by ops/csrc/string_sort.hip; off =
     # the host code, one Python object per row (env SAIL_EXEC_STRING_SORT,

@@ -1158,7 +1158,8 @@ class Executor:
             return out
         lchunk = Chunk(lcols, names)
         rchunk = Chunk(rcols, names)
-        _, _, counts = equi_join(rchunk.columns, lchunk.columns, "semi")
+        _, _, counts = equi_join(rchunk.columns, lchunk.columns, "semi",
+                                 counts_only=True)
         if p.op == "intersect":
             mask = counts > 0
         else:  # except
@@ -1786,7 +1787,10 @@ def join_chunks(ev: Evaluator, p: S.Join, left: Chunk, right: Chunk) -> Chunk:
     rkeys = [right.columns[j - len(left.columns)] for _, j in equi]
 
     # orient: build on right, probe on left
-    probe_idx, build_idx, counts = equi_join(rkeys, lkeys, how)
+    # semi/anti without a residual only ask whether a probe row matched
+    probe_idx, build_idx, counts = equi_join(
+        rkeys, lkeys, how,
+        counts_only=how in ("semi", "anti") and residual is None)
 
     if residual is not None and probe_idx.shape[0] > 0:
         # gather only the columns the residual references (a q21-style

@@ -11,6 +11,7 @@ exactly (no hash collisions on this path).
 """
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Tuple
 
 import torch
@@ -122,9 +123,12 @@ def dense_ids(build_keys: List[torch.Tensor], probe_keys: List[torch.Tensor]):
 
 
 def _expand_matches(bids: torch.Tensor, pids: torch.Tensor,
-                    b_valid: Optional[torch.Tensor], p_valid: Optional[torch.Tensor]):
+                    b_valid: Optional[torch.Tensor], p_valid: Optional[torch.Tensor],
+                    counts_only: bool = False):
     """Core equi-match: returns (probe_idx, build_idx) pairs for all matches,
-    plus per-probe match counts and build-side matched flags."""
+    plus per-probe match counts and build-side matched flags. `counts_only`
+    says the caller compares counts with 0 and nothing else: the device path
+    may then return no pairs (None, None) and counts of 0/1."""
     nb, np_ = bids.shape[0], pids.shape[0]
     dev = bids.device
     # null sentinels at the extreme of the int64 domain so they can never
@@ -147,7 +151,7 @@ def _expand_matches(bids: torch.Tensor, pids: torch.Tensor,
         from ..ops import kernels as K
 
         if K.available():
-            return _expand_matches_gpu(bids, pids, K.require())
+            return _expand_matches_gpu(bids, pids, K.require(), counts_only)
     order = torch.argsort(bids)
     bsorted = bids[order]
     lo = torch.searchsorted(bsorted, pids, right=False)
@@ -168,8 +172,12 @@ def _expand_matches(bids: torch.Tensor, pids: torch.Tensor,
 
 
 def equi_join(build_keys: List[Column], probe_keys: List[Column], how: str,
+              counts_only: bool = False,
               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
-    """Returns (probe_indices, build_indices, probe_unmatched_mask).
+    """Returns (probe_indices, build_indices, counts per probe row).
+
+    `counts_only`: the caller only tests counts against 0 (semi/anti without
+    a residual, INTERSECT/EXCEPT); the pairs may then come back as None.
 
     how semantics are relative to (build=right side? no): caller orients.
     - "inner": matched pairs only
@@ -192,7 +200,7 @@ def equi_join(build_keys: List[Column], probe_keys: List[Column], how: str,
         if c.validity is not None:
             m = c.valid_mask()
             pv = m if pv is None else (pv & m)
-    probe_idx, build_idx, counts = _expand_matches(bids, pids, bv, pv)
+    probe_idx, build_idx, counts = _expand_matches(bids, pids, bv, pv, counts_only)
     return probe_idx, build_idx, counts
 
 
@@ -413,9 +421,66 @@ def exact_string_codes(cols) -> list:
     return out
 
 
-def _expand_matches_gpu(bids: torch.Tensor, pids: torch.Tensor, ext):
-    """HIP open-addressing hash join (ops/csrc/hash_join.hip): chain build +
-    two-phase count/fill probe. Same contract as the sort-based matcher."""
+def join_fused_enabled() -> bool:
+    """SAIL_EXEC_JOIN_FUSED (config sail.exec.join_fused), default on: the
+    device join looks every probe row up once (hj_probe_heads /
+    hj_probe_exists). `off`, `0` or `false` selects hj_build_chain +
+    hj_probe_count + hj_probe_fill. Read on every join, so one process can
+    alternate the two."""
+    v = os.environ.get("SAIL_EXEC_JOIN_FUSED")
+    return v is None or v.lower() not in ("off", "false", "0")
+
+
+# which way each device join went: `unique` (no build key repeats, one
+# lookup per probe row), `chained` (repeats: heads + counts, then a fill that
+# walks next[] only), `exists` (counts only, no pairs), `legacy` (switch off)
+JOIN_PATHS = {"unique": 0, "chained": 0, "exists": 0, "legacy": 0}
+LAST_JOIN_PATH: Optional[str] = None
+
+
+def _took(path: str) -> None:
+    global LAST_JOIN_PATH
+    JOIN_PATHS[path] += 1
+    LAST_JOIN_PATH = path
+
+
+def _expand_matches_gpu(bids: torch.Tensor, pids: torch.Tensor, ext,
+                        counts_only: bool = False):
+    """HIP open-addressing hash join (ops/csrc/hash_join.hip). Same contract
+    as the sort-based matcher: probe_idx non-decreasing, pairs an exact
+    multiset, one count per probe row. With `counts_only` the pairs are None
+    and counts is 0/1 (presence)."""
+    if not join_fused_enabled():
+        _took("legacy")
+        return _expand_matches_gpu_two_pass(bids, pids, ext)
+    bids, pids = bids.contiguous(), pids.contiguous()
+    if counts_only:
+        # presence needs the key slots alone: no heads, no chains, no sync
+        tkeys = ext.hj_build_flag(bids, True)[0]
+        _took("exists")
+        return None, None, ext.hj_probe_exists(tkeys, pids)
+    tkeys, theads, nxt, dup = ext.hj_build_flag(bids, False)
+    # heads[i]: the build row at the head of probe row i's chain, or -1;
+    # counts[i]: its number of matches; stat = [build had repeats, rows matched]
+    heads, counts, stat = ext.hj_probe_heads(tkeys, theads, nxt, dup, pids)
+    repeats, matched = stat.tolist()
+    np_ = pids.shape[0]
+    if repeats:
+        _took("chained")
+        ends = torch.cumsum(counts, 0)
+        total = int(ends[-1].item()) if np_ else 0
+        probe_idx, build_idx = ext.hj_fill_heads(heads, ends, nxt, total)
+        return probe_idx, build_idx, counts
+    _took("unique")
+    if matched == np_:
+        return torch.arange(np_, device=pids.device), heads, counts
+    # ascending positions: the order the count/fill path emits
+    probe_idx = torch.nonzero(counts, as_tuple=False).squeeze(1)
+    return probe_idx, heads.index_select(0, probe_idx), counts
+
+
+def _expand_matches_gpu_two_pass(bids: torch.Tensor, pids: torch.Tensor, ext):
+    """Chain build + two-phase count/fill probe (sail.exec.join_fused=off)."""
     tkeys, theads, nxt = ext.hj_build_chain(bids)
     counts32 = ext.hj_probe_count(tkeys, theads, nxt, pids)
     counts = counts32.to(torch.int64)

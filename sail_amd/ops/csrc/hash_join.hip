@@ -12,6 +12,10 @@
 //  * hj_probe_count + hj_probe_fill: two-phase multi-match probe for
 //                     duplicate-key builds (counts -> exclusive scan by the
 //                     caller -> fill), replacing sort+searchsorted entirely.
+//  * hj_build_flag + hj_probe_heads (+ hj_fill_heads), hj_probe_exists: one
+//                     table lookup per probe row (sail.exec.join_fused); the
+//                     build says whether a key repeated, and a build without
+//                     repeats or a presence test needs no second pass.
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
@@ -158,6 +162,106 @@ __global__ void hj_probe_fill_kernel(const int64_t* __restrict__ keys, int64_t n
   }
 }
 
+// ------------------------------------------------------------------
+// one-lookup probe (sail.exec.join_fused): the table is searched once per
+// probe row, and a build without repeated keys needs no second pass at all
+// ------------------------------------------------------------------
+
+// Chain build that also reports whether any key repeated: the head exchange
+// returns a row instead of -1 exactly when the key was inserted before (the
+// empty-marker key in slot tmask + 1 and the null sentinel included). With
+// kKeysOnly the table is built for presence tests: key slots alone.
+template <bool kKeysOnly>
+__global__ void hj_build_flag_kernel(const int64_t* __restrict__ keys, int64_t n,
+                                     int64_t* __restrict__ tkeys,
+                                     int64_t* __restrict__ theads, int64_t tmask,
+                                     int64_t* __restrict__ next,
+                                     int* __restrict__ dup_flag) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += gridDim.x * (int64_t)blockDim.x) {
+    bool first;
+    int64_t h = claim_slot(tkeys, keys[i], tmask, &first);
+    if (kKeysOnly) continue;
+    long long old = atomicExch((unsigned long long*)&theads[h],
+                               (unsigned long long)i);
+    next[i] = old;  // -1 for the first row of a key
+    if (old != -1) *dup_flag = 1;
+  }
+}
+
+// Sum `v` over the wave; every lane of the wave must call it.
+__device__ inline unsigned long long wave_sum(unsigned long long v) {
+  for (int d = warpSize / 2; d > 0; d >>= 1) v += __shfl_down(v, d);
+  return v;
+}
+
+// One table lookup per probe row. heads[i] is the head of the row's chain
+// (for a build without repeats: THE build row) or -1, counts[i] its number of
+// matches; the chain is walked for the count only when the build had
+// repeats. stat[0] <- the build's repeat flag, stat[1] += rows that matched
+// (one atomic per wave).
+__global__ void hj_probe_heads_kernel(const int64_t* __restrict__ keys, int64_t n,
+                                      const int64_t* __restrict__ tkeys,
+                                      const int64_t* __restrict__ theads,
+                                      const int64_t* __restrict__ next,
+                                      int64_t tmask,
+                                      const int* __restrict__ dup_flag,
+                                      int64_t* __restrict__ heads,
+                                      int64_t* __restrict__ counts,
+                                      unsigned long long* __restrict__ stat) {
+  const bool chained = *dup_flag != 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) stat[0] = chained ? 1ull : 0ull;
+  unsigned long long matched = 0;
+  // the loop bound is the same for the whole workgroup: all lanes reach wave_sum
+  for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base < n;
+       base += gridDim.x * (int64_t)blockDim.x) {
+    int64_t i = base + threadIdx.x;
+    if (i >= n) continue;
+    int64_t h = find_slot(tkeys, keys[i], tmask);
+    int64_t head = h >= 0 ? theads[h] : -1;
+    int64_t c = head >= 0 ? 1 : 0;
+    if (chained && head >= 0)
+      for (int64_t r = next[head]; r >= 0; r = next[r]) ++c;
+    heads[i] = head;
+    counts[i] = c;
+    matched += head >= 0 ? 1 : 0;
+  }
+  matched = wave_sum(matched);
+  if ((threadIdx.x & (warpSize - 1)) == 0 && matched)
+    atomicAdd(&stat[1], matched);
+}
+
+// Presence only: counts[i] = 1 when the key is in the table, else 0.
+__global__ void hj_probe_exists_kernel(const int64_t* __restrict__ keys, int64_t n,
+                                       const int64_t* __restrict__ tkeys,
+                                       int64_t tmask,
+                                       int64_t* __restrict__ counts) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += gridDim.x * (int64_t)blockDim.x)
+    counts[i] = find_slot(tkeys, keys[i], tmask) >= 0 ? 1 : 0;
+}
+
+// Emit the pairs of a build with repeats from the heads: no table lookup.
+// ends is the inclusive scan of counts; row i writes [ends[i-1], ends[i]) in
+// chain order, the order hj_probe_fill_kernel writes.
+__global__ void hj_fill_heads_kernel(const int64_t* __restrict__ heads,
+                                     const int64_t* __restrict__ ends, int64_t n,
+                                     const int64_t* __restrict__ next,
+                                     int64_t* __restrict__ out_probe,
+                                     int64_t* __restrict__ out_build) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += gridDim.x * (int64_t)blockDim.x) {
+    int64_t r = heads[i];
+    if (r < 0) continue;
+    int64_t o = i ? ends[i - 1] : 0;
+    for (; r >= 0; r = next[r]) {
+      out_probe[o] = i;
+      out_build[o] = r;
+      ++o;
+    }
+  }
+}
+
 int64_t table_size_for(int64_t n) {
   int64_t sz = 64;
   while (sz < 2 * n) sz <<= 1;
@@ -290,6 +394,91 @@ std::vector<torch::Tensor> hj_probe_fill(torch::Tensor tkeys, torch::Tensor thea
   return {out_probe, out_build};
 }
 
+// {tkeys, theads, next, dup}: the chain table of hj_build_chain plus a
+// one-element flag that is 1 when some key occurred twice. keys_only builds
+// the key slots alone (for hj_probe_exists) and returns {tkeys}.
+std::vector<torch::Tensor> hj_build_flag(torch::Tensor keys, bool keys_only) {
+  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64 && keys.is_contiguous());
+  int64_t n = keys.numel();
+  int64_t sz = table_size_for(std::max<int64_t>(n, 1));
+  auto tkeys = torch::full({sz + 1}, kEmpty, keys.options());
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  if (keys_only) {
+    if (n)
+      hipLaunchKernelGGL(hj_build_flag_kernel<true>, dim3(grid_for(n)), dim3(kBlock), 0,
+                         stream, keys.data_ptr<int64_t>(), n, tkeys.data_ptr<int64_t>(),
+                         (int64_t*)nullptr, sz - 1, (int64_t*)nullptr, (int*)nullptr);
+    return {tkeys};
+  }
+  auto theads = torch::full({sz + 1}, -1, keys.options());
+  auto next = torch::empty({std::max<int64_t>(n, 1)}, keys.options());
+  auto dup = torch::zeros({1}, keys.options().dtype(torch::kInt32));
+  if (n)
+    hipLaunchKernelGGL(hj_build_flag_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0,
+                       stream, keys.data_ptr<int64_t>(), n, tkeys.data_ptr<int64_t>(),
+                       theads.data_ptr<int64_t>(), sz - 1, next.data_ptr<int64_t>(),
+                       dup.data_ptr<int32_t>());
+  return {tkeys, theads, next, dup};
+}
+
+// {heads, counts, stat}: see hj_probe_heads_kernel. stat is int64[2] =
+// {build had repeats, probe rows that matched}.
+std::vector<torch::Tensor> hj_probe_heads(torch::Tensor tkeys, torch::Tensor theads,
+                                          torch::Tensor next, torch::Tensor dup,
+                                          torch::Tensor keys) {
+  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64 && keys.is_contiguous());
+  TORCH_CHECK(theads.numel() == tkeys.numel() && dup.numel() == 1 &&
+              dup.scalar_type() == torch::kInt32);
+  int64_t n = keys.numel();
+  auto heads = torch::empty({n}, keys.options());
+  auto counts = torch::empty({n}, keys.options());
+  auto stat = torch::zeros({2}, keys.options());
+  if (n) {
+    hipStream_t stream = c10::hip::getCurrentHIPStream();
+    hipLaunchKernelGGL(hj_probe_heads_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream,
+                       keys.data_ptr<int64_t>(), n, tkeys.data_ptr<int64_t>(),
+                       theads.data_ptr<int64_t>(), next.data_ptr<int64_t>(),
+                       tmask_of(tkeys), dup.data_ptr<int32_t>(),
+                       heads.data_ptr<int64_t>(), counts.data_ptr<int64_t>(),
+                       (unsigned long long*)stat.data_ptr<int64_t>());
+  } else {
+    stat.slice(0, 0, 1).copy_(dup);  // no probe rows: the flag still says what the build was
+  }
+  return {heads, counts, stat};
+}
+
+torch::Tensor hj_probe_exists(torch::Tensor tkeys, torch::Tensor keys) {
+  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64 && keys.is_contiguous());
+  int64_t n = keys.numel();
+  auto counts = torch::empty({n}, keys.options());
+  if (n) {
+    hipStream_t stream = c10::hip::getCurrentHIPStream();
+    hipLaunchKernelGGL(hj_probe_exists_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream,
+                       keys.data_ptr<int64_t>(), n, tkeys.data_ptr<int64_t>(),
+                       tmask_of(tkeys), counts.data_ptr<int64_t>());
+  }
+  return counts;
+}
+
+// {probe_idx, build_idx} from the heads and the inclusive scan of the counts
+// (total = ends[n - 1], read by the caller).
+std::vector<torch::Tensor> hj_fill_heads(torch::Tensor heads, torch::Tensor ends,
+                                         torch::Tensor next, int64_t total) {
+  TORCH_CHECK(heads.is_cuda() && heads.scalar_type() == torch::kInt64 &&
+              ends.scalar_type() == torch::kInt64 && ends.numel() == heads.numel() &&
+              heads.is_contiguous() && ends.is_contiguous());
+  int64_t n = heads.numel();
+  auto out_probe = torch::empty({total}, heads.options());
+  auto out_build = torch::empty({total}, heads.options());
+  if (n && total) {
+    hipStream_t stream = c10::hip::getCurrentHIPStream();
+    hipLaunchKernelGGL(hj_fill_heads_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream,
+                       heads.data_ptr<int64_t>(), ends.data_ptr<int64_t>(), n,
+                       next.data_ptr<int64_t>(), out_probe.data_ptr<int64_t>(),
+                       out_build.data_ptr<int64_t>());
+  }
+  return {out_probe, out_build};
+}
 
 std::vector<torch::Tensor> hg_group(torch::Tensor keys) {
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64);

@@ -34,6 +34,13 @@ torch::Tensor hj_probe_count(torch::Tensor tkeys, torch::Tensor theads,
 std::vector<torch::Tensor> hj_probe_fill(torch::Tensor tkeys, torch::Tensor theads,
                                          torch::Tensor next, torch::Tensor keys,
                                          torch::Tensor offsets, int64_t total);
+std::vector<torch::Tensor> hj_build_flag(torch::Tensor keys, bool keys_only);
+std::vector<torch::Tensor> hj_probe_heads(torch::Tensor tkeys, torch::Tensor theads,
+                                          torch::Tensor next, torch::Tensor dup,
+                                          torch::Tensor keys);
+torch::Tensor hj_probe_exists(torch::Tensor tkeys, torch::Tensor keys);
+std::vector<torch::Tensor> hj_fill_heads(torch::Tensor heads, torch::Tensor ends,
+                                         torch::Tensor next, int64_t total);
 std::vector<torch::Tensor> hg_group(torch::Tensor keys);
 // parquet_decode.hip
 torch::Tensor pq_rle_decode(torch::Tensor buf, torch::Tensor pages, int64_t total);
@@ -124,6 +131,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hj_build_chain", &hj_build_chain, "hash join build with chains");
   m.def("hj_probe_count", &hj_probe_count, "hash join probe, count matches");
   m.def("hj_probe_fill", &hj_probe_fill, "hash join probe, emit match pairs");
+  m.def("hj_build_flag", &hj_build_flag, "hash join chain build + repeated-key flag");
+  m.def("hj_probe_heads", &hj_probe_heads, "hash join probe, one lookup: heads, counts, stat");
+  m.def("hj_probe_exists", &hj_probe_exists, "hash join probe, presence as 0/1 counts");
+  m.def("hj_fill_heads", &hj_fill_heads, "emit match pairs from chain heads");
   m.def("hg_group", &hg_group, "hash group-id assignment (sort-free group_ids)");
   m.def("pq_rle_decode", &pq_rle_decode, "parquet RLE/bit-packed hybrid decode");
   m.def("pq_plain_copy", &pq_plain_copy, "parquet PLAIN fixed-width page copy");

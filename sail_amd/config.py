@@ -28,6 +28,11 @@ DEFAULTS: Dict[str, str] = {
     # scatter_reduce_, one call per aggregate (env SAIL_EXEC_AGG_GLOBAL, read
     # on every aggregate)
     "sail.exec.agg_global": "on",
+    # COUNT / SUM / AVG (DISTINCT x) on the device through distinct_acc
+    # (ops/csrc/distinct_agg.hip): one pass over a hash set of (group, value)
+    # pairs, also inside a fused aggregate list; off = two argsorts and one
+    # index_add_ per output (env SAIL_EXEC_DISTINCT_HASH, read at each use)
+    "sail.exec.distinct_hash": "on",
     # device equi-joins look each probe row up once (hj_probe_heads /
     # hj_probe_exists, ops/csrc/hash_join.hip): unique builds and
     # existence-only joins skip the count/scan/fill passes; off = chain build

@@ -207,6 +207,11 @@ def agg_eval(name: str, args: List[Column], gid: torch.Tensor, ng: int,
     c = args[0]
     mask = _masked(c, filter_mask)
     if distinct and name in ("count", "sum", "avg"):
+        ext = _distinct_ext(name, c, gid, ng)
+        if ext is not None:
+            return _distinct_finish(name, _distinct_hash(ext, c, gid, ng, mask, name != "count"),
+                                    c, out_type)
+        _took_distinct("sort")
         # unique (gid, value) pairs via two stable sorts — torch.unique(dim=0)
         # has an allocation-state-dependent crash on ROCm at ~1e8 rows
         vk = normalize_key(c)
@@ -784,9 +789,81 @@ def _acc_global(ext, gid, mask, vals, ops, ng):
     return ext.grouped_acc_global(gid, mask, vals, ops, ng)
 
 
+# ---------------------------------------------------------------------------
+# COUNT / SUM / AVG (DISTINCT x) (ops/csrc/distinct_agg.hip)
+# ---------------------------------------------------------------------------
+
+def distinct_hash_enabled() -> bool:
+    """SAIL_EXEC_DISTINCT_HASH (config sail.exec.distinct_hash), default on:
+    count/sum/avg DISTINCT on the device go through distinct_acc, one pass
+    over a hash set of (group, value) pairs. `off`, `0` or `false` selects the
+    two sorts. Read at each use, so one process can alternate the two."""
+    v = os.environ.get("SAIL_EXEC_DISTINCT_HASH")
+    return v is None or v.lower() not in ("off", "false", "0")
+
+
+# which way each distinct count/sum/avg went: `hash` (distinct_acc) or `sort`
+# (two argsorts and index_add_: a host column, the switch off, a float sum, a
+# table above half of the free device memory)
+DISTINCT_PATHS = {"hash": 0, "sort": 0}
+LAST_DISTINCT_PATH: Optional[str] = None
+
+
+def _took_distinct(path: str) -> None:
+    global LAST_DISTINCT_PATH
+    DISTINCT_PATHS[path] += 1
+    LAST_DISTINCT_PATH = path
+
+
+_INT_STORAGE = (torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def _distinct_ext(name: str, c: Column, gid: torch.Tensor, ng: int):
+    """The extension when distinct_acc may serve this aggregate, else None."""
+    n = gid.shape[0]
+    if not gid.is_cuda or not distinct_hash_enabled() or n >= (1 << 32) - 1 \
+            or not 1 <= ng < (1 << 31):
+        return None
+    if name != "count" and (isinstance(c, StringColumn) or c.data.dtype not in _INT_STORAGE):
+        return None  # sums of ints, decimals and dates only
+    from ..ops import kernels as K
+
+    if not K.available():
+        return None
+    ext = K.require()
+    if not hasattr(ext, "distinct_acc"):
+        return None
+    # the table: 2n slots rounded up to a power of two, 8 B each for one
+    # group and 4 B otherwise; above half of the free memory the sorts stay.
+    # The driver is asked only for tables above 256 MiB: the query costs more
+    # than a small aggregate, and the sorts need several times the table
+    slots = max(64, 1 << (2 * n - 1).bit_length()) if n else 64
+    table = slots * (8 if ng == 1 else 4)
+    if table > (1 << 28) and table > torch.cuda.mem_get_info(gid.device)[0] // 2:
+        return None
+    return ext
+
+
+def _distinct_hash(ext, c: Column, gid: torch.Tensor, ng: int, mask: torch.Tensor,
+                   want_sum: bool) -> torch.Tensor:
+    """One distinct_acc launch -> int64 [2, ng]: distinct count, distinct sum."""
+    _took_distinct("hash")
+    return ext.distinct_acc(None if ng == 1 else gid.contiguous(),
+                            normalize_key(c).contiguous(), mask.contiguous(), ng, want_sum)
+
+
+def _distinct_finish(name: str, acc: torch.Tensor, c: Column, out_type) -> Column:
+    if name == "count":
+        return Column(T.I64, acc[0], None)
+    if name == "avg":
+        return _avg_result(acc[1], acc[0], c.dtype, out_type)
+    return Column(out_type or T.I64, acc[1], None)
+
+
 def fused_agg_batch(aggs, args_list, fmasks, gid: torch.Tensor, ng: int):
     """Evaluate a whole aggregate list in one (or few) fused kernel passes:
-    grouped_acc up to 4096 groups, grouped_acc_global above.
+    grouped_acc up to 4096 groups, grouped_acc_global above. A DISTINCT
+    count/sum/avg in the list is one distinct_acc launch of its own.
 
     aggs: list of S.AggFunc; args_list[i]: evaluated arg Columns;
     fmasks[i]: optional bool mask (FILTER clause). Returns list[Column] or
@@ -809,6 +886,11 @@ def fused_agg_batch(aggs, args_list, fmasks, gid: torch.Tensor, ng: int):
     plans = []
     for a, args, fm in zip(aggs, args_list, fmasks):
         name = a.name
+        if a.distinct and name in ("count", "sum", "avg") and args:
+            if _distinct_ext(name, args[0], gid, ng) is None:
+                return None
+            plans.append(("distinct", None, None, (args[0], fm), a))
+            continue
         if a.distinct or name not in ("sum", "try_sum", "count", "count_if",
                                       "avg", "try_avg", "min", "max"):
             return None
@@ -890,6 +972,11 @@ def fused_agg_batch(aggs, args_list, fmasks, gid: torch.Tensor, ng: int):
     # finalize per agg
     out_cols: List[Column] = []
     for kind, mkey, vidx, extra, a in plans:
+        if kind == "distinct":
+            c, fm = extra  # its own mask: validity & FILTER
+            acc = _distinct_hash(ext, c, gid, ng, _masked(c, fm), a.name != "count")
+            out_cols.append(_distinct_finish(a.name, acc, c, a.dtype))
+            continue
         outs = results[mkey]
         if kind == "count":
             out_cols.append(Column(T.I64, outs[vidx]))

@@ -25,6 +25,10 @@ torch::Tensor grouped_acc(torch::Tensor gid, c10::optional<torch::Tensor> mask,
 torch::Tensor grouped_acc_global(torch::Tensor gid, c10::optional<torch::Tensor> mask,
                                  std::vector<c10::optional<torch::Tensor>> vals,
                                  std::vector<int64_t> ops, int64_t G, int64_t variant);
+// distinct_agg.hip
+torch::Tensor distinct_acc(c10::optional<torch::Tensor> gid, torch::Tensor keys,
+                           c10::optional<torch::Tensor> mask, int64_t ng, bool want_sum,
+                           int64_t table_slots, int64_t variant);
 // hash_join.hip
 std::vector<torch::Tensor> hj_build(torch::Tensor keys);
 torch::Tensor hj_probe_unique(torch::Tensor tkeys, torch::Tensor tvals, torch::Tensor keys);
@@ -126,6 +130,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       "int64 gid; variant 1 / 2 switch run combining / the LDS cache off",
       py::arg("gid"), py::arg("mask"), py::arg("vals"), py::arg("ops"), py::arg("G"),
       py::arg("variant") = 0);
+  // distinct_agg.hip: cases in tests/test_distinct_acc.py
+  m.def(
+      "distinct_acc", &distinct_acc,
+      "count and sum of the distinct (gid, key) pairs per group -> int64 [2, ng]; gid "
+      "None means ng == 1; table_slots is a power of two above the row count; variant "
+      "bit 0 switches the wave filter off, bit 1 the LDS cache on",
+      py::arg("gid"), py::arg("keys"), py::arg("mask"), py::arg("ng"), py::arg("want_sum"),
+      py::arg("table_slots") = 0, py::arg("variant") = 0);
   m.def("hj_build", &hj_build, "hash join build (unique keys)");
   m.def("hj_probe_unique", &hj_probe_unique, "hash join probe, first match");
   m.def("hj_build_chain", &hj_build_chain, "hash join build with chains");

@@ -33,6 +33,11 @@ DEFAULTS: Dict[str, str] = {
     # pairs, also inside a fused aggregate list; off = two argsorts and one
     # index_add_ per output (env SAIL_EXEC_DISTINCT_HASH, read at each use)
     "sail.exec.distinct_hash": "on",
+    # median / percentile / percentile_disc over a device column stay on the
+    # device: radix select per group (grouped_select,
+    # ops/csrc/grouped_select.hip), device sorts above its histogram budget;
+    # off = the host loop (env SAIL_EXEC_PERCENTILE_SELECT, read at each use)
+    "sail.exec.percentile_select": "on",
     # device equi-joins look each probe row up once (hj_probe_heads /
     # hj_probe_exists, ops/csrc/hash_join.hip): unique builds and
     # existence-only joins skip the count/scan/fill passes; off = chain build

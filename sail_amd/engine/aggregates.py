@@ -270,6 +270,12 @@ def agg_eval(name: str, args: List[Column], gid: torch.Tensor, ng: int,
         torch.cumsum(lens, 0, out=offs[1:])
         return ListColumn(offs, c.gather(kept))
 
+    if name in ("median", "percentile", "percentile_approx", "percentile_disc"):
+        out = _percentile_device(name, args, c, gid, ng, mask)
+        if out is not None:
+            return out
+        _took_percentile("host")
+
     gidm = gid[mask]
     n_used = int(mask.sum().item())
 
@@ -528,7 +534,6 @@ def agg_eval(name: str, args: List[Column], gid: torch.Tensor, ng: int,
             vals = vals / (10.0 ** c.dtype.scale)
         out = torch.zeros(ng, dtype=torch.float64, device=dev)
         g = gidm
-        order = torch.argsort(g * (2 ** 20) + torch.argsort(torch.argsort(vals)))
         # simple per-group via host loop fallback (reference correctness path)
         import numpy as np
 
@@ -850,6 +855,116 @@ def _distinct_hash(ext, c: Column, gid: torch.Tensor, ng: int, mask: torch.Tenso
     _took_distinct("hash")
     return ext.distinct_acc(None if ng == 1 else gid.contiguous(),
                             normalize_key(c).contiguous(), mask.contiguous(), ng, want_sum)
+
+
+# ---------------------------------------------------------------------------
+# median / percentile / percentile_disc (ops/csrc/grouped_select.hip)
+# ---------------------------------------------------------------------------
+
+def percentile_select_enabled() -> bool:
+    """SAIL_EXEC_PERCENTILE_SELECT (config sail.exec.percentile_select),
+    default on: median, percentile and percentile_disc over a device column
+    stay on the device (grouped_select, or two sorts above its histogram
+    budget). `off`, `0` or `false` selects the host loop. Read at each use, so
+    one process can alternate them."""
+    v = os.environ.get("SAIL_EXEC_PERCENTILE_SELECT")
+    return v is None or v.lower() not in ("off", "false", "0")
+
+
+# which way each median/percentile went: `select` (grouped_select), `sort`
+# (device sorts: more groups than the histogram budget holds) or `host` (a
+# host column, the switch off, non-numeric input, no extension)
+PERCENTILE_PATHS = {"select": 0, "sort": 0, "host": 0}
+LAST_PERCENTILE_PATH: Optional[str] = None
+
+#: bytes of grouped_select's [ng][256] uint32 bins above which `sort` serves
+#: (the binding's own limit; tools/percentile_bench.py is where it comes from)
+PERCENTILE_HIST_BUDGET = 1 << 28
+
+
+def _took_percentile(path: str) -> None:
+    global LAST_PERCENTILE_PATH
+    PERCENTILE_PATHS[path] += 1
+    LAST_PERCENTILE_PATH = path
+
+
+def _percentile_device(name: str, args: List[Column], c: Column, gid: torch.Tensor, ng: int,
+                       mask: torch.Tensor) -> Optional[Column]:
+    """median / percentile / percentile_disc without leaving the device, or
+    None where the host code has to serve."""
+    n = gid.shape[0]
+    if not gid.is_cuda or not percentile_select_enabled() or type(c) is not Column \
+            or c.data.dtype not in _INT_STORAGE + (torch.float32, torch.float64) \
+            or n == 0 or n >= (1 << 32) - 1 or ng < 1:
+        return None
+    from ..ops import kernels as K
+
+    ext = K.require() if K.available() else None
+    if not hasattr(ext, "grouped_select"):
+        return None
+    disc = name == "percentile_disc"
+    q = 0.5
+    if name != "median" and len(args) > 1 and len(args[1]):
+        q = float(args[1].to_pylist()[0])
+    desc = name != "median" and len(args) > 2 and len(args[2]) and bool(args[2].to_pylist()[0])
+    if not disc and desc:
+        q = 1.0 - q  # WITHIN GROUP (ORDER BY x DESC)
+    if not 0.0 <= q <= 1.0:
+        return None  # the host code words the error
+    mode = 0 if not disc else (2 if desc else 1)
+    qq = (q * 100) / 100  # numpy's own rounding of the percentage
+    vals = c.data.to(torch.float64)
+    if isinstance(c.dtype, T.DecimalType) and not disc:
+        vals = vals / (10.0 ** c.dtype.scale)
+    if ng * 1024 <= PERCENTILE_HIST_BUDGET:
+        _took_percentile("select")
+        lo_hi, meta = ext.grouped_select(vals.contiguous(), None if ng == 1 else gid.contiguous(),
+                                         mask.contiguous(), ng, q, mode, qq)
+        lo, hi, cnt, row, nan = lo_hi[0], lo_hi[1], meta[0], meta[1].clamp_min(0), meta[2] != 0
+    else:
+        _took_percentile("sort")
+        lo, hi, cnt, row, nan = _percentile_sort(vals, gid, ng, mask, q, qq, mode)
+
+    if disc:
+        out = c.gather(row)
+        has = cnt > 0
+        if not bool(has.all()):
+            out = Column(out.dtype, out.data, (out.valid_mask() & has).to(torch.uint8))
+        return out
+    # numpy's linear rule, one rounding per step as numpy has it
+    vi = qq * (cnt - 1).clamp_min(0).to(torch.float64)
+    t = vi - torch.floor(vi)
+    d = hi - lo
+    r = torch.where(t >= 0.5, hi - d * (1 - t), lo + d * t)
+    r = torch.where(nan, torch.full_like(r, float("nan")), r)
+    return Column(T.F64, torch.where(cnt == 0, torch.zeros_like(r), r), None)
+
+
+def _percentile_sort(vals, gid, ng, mask, q, qq, mode):
+    """What grouped_select returns, from two device sorts: rows ordered by
+    (group, value, row), group starts from a bincount, two gathers."""
+    rows = torch.nonzero(mask, as_tuple=False).flatten()
+    v, g = vals[rows], gid[rows]
+    o = torch.argsort(v, stable=True)            # NaNs last, as numpy sorts them
+    o = o[torch.argsort(g[o], stable=True)]
+    v, rows = v[o], rows[o]
+    cnt = torch.bincount(g, minlength=ng)
+    start = torch.cumsum(cnt, 0) - cnt
+    last = (cnt - 1).clamp_min(0)
+    if mode == 0:
+        k = torch.floor(qq * last.to(torch.float64)).to(torch.int64)
+    else:
+        k = (torch.ceil(q * cnt.to(torch.float64)) - 1).to(torch.int64).clamp_min(0)
+    k = torch.minimum(k, last)
+    if mode == 2:
+        k = last - k
+    if v.numel() == 0:
+        z = torch.zeros(ng, dtype=torch.float64, device=vals.device)
+        return z, z, cnt, cnt, cnt != 0
+    top = v.numel() - 1
+    at = lambda i: (start + i).clamp_max(top)    # an empty group reads any row
+    return (v[at(k)], v[at(torch.minimum(k + 1, last))], cnt, rows[at(k)],
+            torch.isnan(v[at(last)]) & (cnt > 0))
 
 
 def _distinct_finish(name: str, acc: torch.Tensor, c: Column, out_type) -> Column:

@@ -29,6 +29,10 @@ torch::Tensor grouped_acc_global(torch::Tensor gid, c10::optional<torch::Tensor>
 torch::Tensor distinct_acc(c10::optional<torch::Tensor> gid, torch::Tensor keys,
                            c10::optional<torch::Tensor> mask, int64_t ng, bool want_sum,
                            int64_t table_slots, int64_t variant);
+// grouped_select.hip
+std::vector<torch::Tensor> grouped_select(torch::Tensor vals, c10::optional<torch::Tensor> gid,
+                                          c10::optional<torch::Tensor> mask, int64_t ng,
+                                          double q, int64_t mode, double qq);
 // hash_join.hip
 std::vector<torch::Tensor> hj_build(torch::Tensor keys);
 torch::Tensor hj_probe_unique(torch::Tensor tkeys, torch::Tensor tvals, torch::Tensor keys);
@@ -138,6 +142,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       "bit 0 switches the wave filter off, bit 1 the LDS cache on",
       py::arg("gid"), py::arg("keys"), py::arg("mask"), py::arg("ng"), py::arg("want_sum"),
       py::arg("table_slots") = 0, py::arg("variant") = 0);
+  // grouped_select.hip: cases in tests/test_grouped_select.py
+  m.def(
+      "grouped_select", &grouped_select,
+      "value at the wanted rank of each group's sorted float64 values and the value after "
+      "it -> (float64 [2, ng] lo and hi, int64 [3, ng] row count, smallest row holding lo, "
+      "NaN flag); gid None means ng == 1; mode 0 continuous (rank floor(qq * (count - 1)), "
+      "qq defaults to q), 1 discrete ascending, 2 discrete descending",
+      py::arg("vals"), py::arg("gid"), py::arg("mask"), py::arg("ng"), py::arg("q"),
+      py::arg("mode"), py::arg("qq") = -1.0);
   m.def("hj_build", &hj_build, "hash join build (unique keys)");
   m.def("hj_probe_unique", &hj_probe_unique, "hash join probe, first match");
   m.def("hj_build_chain", &hj_build_chain, "hash join build with chains");

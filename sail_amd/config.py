@@ -38,6 +38,11 @@ DEFAULTS: Dict[str, str] = {
     # ops/csrc/grouped_select.hip), device sorts above its histogram budget;
     # off = the host loop (env SAIL_EXEC_PERCENTILE_SELECT, read at each use)
     "sail.exec.percentile_select": "on",
+    # MIN / MAX over a ROWS or RANGE window frame of a device column by
+    # window_frame_minmax (ops/csrc/window_frames.hip): wave scans per 64-row
+    # block and a sparse table over blocks; off = a sparse table over rows in
+    # torch (env SAIL_EXEC_WINDOW_FRAMES, read at each use)
+    "sail.exec.window_frames": "on",
     # device equi-joins look each probe row up once (hj_probe_heads /
     # hj_probe_exists, ops/csrc/hash_join.hip): unique builds and
     # existence-only joins skip the count/scan/fill passes; off = chain build

@@ -1,13 +1,22 @@
-"""Window function evaluation (torch path).
+"""Window function evaluation.
 
-Partition/order by sort, then per-function segment ops
+Partition/order by sort, then per-function segment ops in torch
 (ref: crates/sail-function/src/window/, DataFusion BoundedWindowAggExec role).
 Supported: row_number, rank, dense_rank, percent_rank, cume_dist, ntile,
-lag/lead, sum/count/min/max/avg over the default or running frame.
+lag/lead, nth_value, and sum/count/avg/min/max/first/last over the default,
+running and whole-partition frames and over ROWS and RANGE frames with literal
+offsets, `ROWS ... AND UNBOUNDED FOLLOWING` included.
+
+MIN and MAX over a ROWS or RANGE frame are a range-min query per row: on the
+device by `window_frame_minmax` (ops/csrc/window_frames.hip; switch
+`sail.exec.window_frames`), on the host and with the switch off by a sparse
+table in torch. Frame sums and counts are prefix sums; running and default-frame
+aggregates are cumulative ops with a per-partition bias.
 """
 from __future__ import annotations
 
-from typing import List
+import os
+from typing import List, Optional
 
 import torch
 
@@ -170,8 +179,8 @@ def eval_window(ev: Evaluator, e: S.WindowExpr, chunk: Chunk) -> Column:
 
 
 def _window_agg(ev, f: S.AggFunc, sorted_chunk, part_id, pos_in_part, e, n, dev):
-    """sum/count/avg/min/max/first/last over whole-partition, running, or
-    bounded-ROWS frames (prefix-sum sliding windows)."""
+    """sum/count/avg/min/max/first/last over whole-partition, running, ROWS
+    or RANGE frames (prefix sums; range-min queries for min and max)."""
     from .aggregates import agg_eval
 
     running = bool(e.order_by) and (e.frame is None or e.frame[1][0] == "unbounded_preceding")
@@ -180,14 +189,15 @@ def _window_agg(ev, f: S.AggFunc, sorted_chunk, part_id, pos_in_part, e, n, dev)
     bounded = (e.frame is not None and e.frame[0] == "rows"
                and not whole
                and e.frame[1][0] in ("preceding", "following", "current", "unbounded_preceding")
-               and e.frame[2][0] in ("preceding", "following", "current"))
+               and e.frame[2][0] in ("preceding", "following", "current",
+                                     "unbounded_following"))
     ng = int(part_id.max().item()) + 1
     args = [broadcast(ev.eval(a, sorted_chunk), n, dev) for a in f.args] if f.args else []
     part_start_pos = torch.nonzero(
         torch.cat([torch.ones(1, dtype=torch.bool, device=dev),
                    part_id[1:] != part_id[:-1]]), as_tuple=False).squeeze(1)
-    if bounded and f.name in ("sum", "count", "avg", "first", "first_value",
-                              "last", "last_value"):
+    if bounded and f.name in ("sum", "count", "avg", "min", "max", "first",
+                              "first_value", "last", "last_value"):
         return _bounded_rows_agg(f, args, part_id, pos_in_part,
                                  part_start_pos, e.frame, n, dev)
     range_bounded = (e.frame is not None and e.frame[0] == "range"
@@ -197,8 +207,9 @@ def _window_agg(ev, f: S.AggFunc, sorted_chunk, part_id, pos_in_part, e, n, dev)
                      and e.frame[2][0] in ("preceding", "following",
                                            "current",
                                            "unbounded_following"))
-    if range_bounded and f.name in ("sum", "count", "avg", "first",
-                                    "first_value", "last", "last_value"):
+    if range_bounded and f.name in ("sum", "count", "avg", "min", "max",
+                                    "first", "first_value", "last",
+                                    "last_value"):
         ok = broadcast(ev.eval(e.order_by[0].child, sorted_chunk), n, dev)
         if ok.data is not None and not isinstance(ok, StringColumn):
             if not e.order_by[0].ascending:
@@ -264,7 +275,14 @@ def _bounded_rows_agg(f, args, part_id, pos_in_part, part_start_pos, frame, n, d
 
     s_pos = torch.maximum(bound_pos(frame[1], True), pstart)
     t_pos = torch.minimum(bound_pos(frame[2], False), pend)
-    return _frame_agg(f, args, s_pos, t_pos, pstart, pend, n, dev)
+    # two literal offsets bound the frame's length whatever the partitions are
+    signed = {"current": lambda v: 0, "preceding": lambda v: -int(v),
+              "following": lambda v: int(v)}
+    max_rows = None
+    if frame[1][0] in signed and frame[2][0] in signed:
+        max_rows = max(signed[frame[2][0]](frame[2][1])
+                       - signed[frame[1][0]](frame[1][1]) + 1, 1)
+    return _frame_agg(f, args, s_pos, t_pos, pstart, pend, n, dev, max_rows)
 
 
 def _bounded_range_agg(f, args, part_id, part_start_pos, frame, order_vals,
@@ -314,7 +332,74 @@ def _bounded_range_agg(f, args, part_id, part_start_pos, frame, order_vals,
     return _frame_agg(f, args, s_pos, t_pos, pstart, pend, n, dev)
 
 
-def _frame_agg(f, args, s_pos, t_pos, pstart, pend, n, dev):
+def window_frames_enabled() -> bool:
+    """SAIL_EXEC_WINDOW_FRAMES (config sail.exec.window_frames), default on:
+    MIN and MAX over a ROWS or RANGE frame of a device column run in
+    window_frame_minmax (ops/csrc/window_frames.hip). `off`, `0` or `false`
+    selects the sparse table in torch. Read at each use, so one process can
+    alternate them."""
+    v = os.environ.get("SAIL_EXEC_WINDOW_FRAMES")
+    return v is None or v.lower() not in ("off", "false", "0")
+
+
+# which way each frame MIN/MAX went: `hip` (window_frame_minmax) or `torch` (a
+# host column, or the switch off)
+WINDOW_PATHS = {"hip": 0, "torch": 0}
+LAST_WINDOW_PATH: Optional[str] = None
+
+
+def _took_window(path: str) -> None:
+    global LAST_WINDOW_PATH
+    WINDOW_PATHS[path] += 1
+    LAST_WINDOW_PATH = path
+
+
+def _frame_minmax(c: Column, valid, s_pos, t_pos, wcnt, is_max: bool,
+                  max_rows: Optional[int]) -> Column:
+    """MIN / MAX of the valid rows s_pos..t_pos (inclusive, s <= t) of `c`,
+    NULL where wcnt is 0. NaN is the largest value (Spark)."""
+    x = c.data.to(torch.float64 if c.data.is_floating_point() else torch.int64)
+    if x.is_cuda and window_frames_enabled():
+        from ..ops import kernels as K
+
+        _took_window("hip")
+        res = K.require().window_frame_minmax(
+            x.contiguous(), None if c.validity is None else valid.contiguous(),
+            s_pos.contiguous(), t_pos.contiguous(), int(is_max), max_rows or 0)
+    else:
+        _took_window("torch")
+        res = _frame_minmax_torch(x, valid, s_pos, t_pos, is_max)
+    vmask = wcnt > 0
+    res = torch.where(vmask, res, torch.zeros_like(res)).to(c.data.dtype)
+    return Column(c.dtype, res, None if bool(vmask.all()) else vmask.to(torch.uint8))
+
+
+def _frame_minmax_torch(x, valid, s_pos, t_pos, is_max: bool):
+    """Sparse table over all rows: level j holds the op over 2^j rows from
+    each row on; a frame of length in [2^j, 2^(j+1)) is two lookups in level
+    j. Invalid rows enter as the identity; fmin skips the NaN identity, so a
+    NaN value stays the largest."""
+    if x.is_floating_point():
+        ident, op = (float("-inf"), torch.maximum) if is_max else (float("nan"), torch.fmin)
+    else:
+        info = torch.iinfo(torch.int64)
+        ident, op = (info.min, torch.maximum) if is_max else (info.max, torch.minimum)
+    level = torch.where(valid, x, torch.full_like(x, ident))
+    # floor(log2(length)) from the exponent frexp returns: length = m * 2^e, m in [0.5, 1)
+    k = torch.frexp((t_pos - s_pos + 1).clamp_min(1).to(torch.float64))[1].to(torch.int64) - 1
+    n = x.shape[0]
+    res = level[s_pos]
+    for j in range(1, int(k.max().item()) + 1):
+        w = 1 << (j - 1)
+        nxt = level.clone()
+        nxt[:n - w] = op(level[:n - w], level[w:])
+        level = nxt
+        hit = op(level[s_pos], level[(t_pos - (1 << j) + 1).clamp_min(0)])
+        res = torch.where(k == j, hit, res)
+    return res
+
+
+def _frame_agg(f, args, s_pos, t_pos, pstart, pend, n, dev, max_rows=None):
     empty = s_pos > t_pos
     s_pos = torch.minimum(s_pos, pend)
     t_pos = torch.maximum(t_pos, pstart)
@@ -341,6 +426,8 @@ def _frame_agg(f, args, s_pos, t_pos, pstart, pend, n, dev):
         return g
 
     c = args[0] if args else None
+    if f.name in ("min", "max") and type(c) is not Column:
+        raise NotImplementedError(f"window frame for {f.name} over a string or nested column")
     valid = c.valid_mask() if c is not None else torch.ones(n, dtype=torch.bool, device=dev)
     vcnt = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     torch.cumsum(valid.to(torch.int64), 0, out=vcnt[1:])
@@ -348,6 +435,8 @@ def _frame_agg(f, args, s_pos, t_pos, pstart, pend, n, dev):
     wcnt = torch.where(empty, torch.zeros_like(wcnt), wcnt)
     if f.name == "count":
         return Column(T.I64, wcnt)
+    if f.name in ("min", "max"):
+        return _frame_minmax(c, valid, s_pos, t_pos, wcnt, f.name == "max", max_rows)
     x = c.data
     x = x.to(torch.float64) if c.dtype.is_float else x.to(torch.int64)
     x = torch.where(valid, x, torch.zeros_like(x))

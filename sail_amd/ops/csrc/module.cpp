@@ -33,6 +33,10 @@ torch::Tensor distinct_acc(c10::optional<torch::Tensor> gid, torch::Tensor keys,
 std::vector<torch::Tensor> grouped_select(torch::Tensor vals, c10::optional<torch::Tensor> gid,
                                           c10::optional<torch::Tensor> mask, int64_t ng,
                                           double q, int64_t mode, double qq);
+// window_frames.hip
+torch::Tensor window_frame_minmax(torch::Tensor x, c10::optional<torch::Tensor> valid,
+                                  torch::Tensor s_pos, torch::Tensor t_pos, int64_t op,
+                                  int64_t max_frame_rows);
 // hash_join.hip
 std::vector<torch::Tensor> hj_build(torch::Tensor keys);
 torch::Tensor hj_probe_unique(torch::Tensor tkeys, torch::Tensor tvals, torch::Tensor keys);
@@ -151,6 +155,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       "qq defaults to q), 1 discrete ascending, 2 discrete descending",
       py::arg("vals"), py::arg("gid"), py::arg("mask"), py::arg("ng"), py::arg("q"),
       py::arg("mode"), py::arg("qq") = -1.0);
+  // window_frames.hip: cases in tests/test_window_frames.py
+  m.def(
+      "window_frame_minmax", &window_frame_minmax,
+      "min (op 0) or max (op 1) of the valid x[s_pos[i] .. t_pos[i]] per row, ends inclusive, "
+      "NaN largest and -0.0 below +0.0 -> tensor like x (int64 or float64); s > t is an empty "
+      "frame (stores 0), a frame without a valid row stores an unspecified value; "
+      "max_frame_rows > 0 bounds t - s + 1 and the table levels built, 0 builds all. Extra "
+      "memory: 16 B per row plus 8 * ceil(n / 64) * (levels + 1)",
+      py::arg("x"), py::arg("valid"), py::arg("s_pos"), py::arg("t_pos"), py::arg("op"),
+      py::arg("max_frame_rows") = 0);
   m.def("hj_build", &hj_build, "hash join build (unique keys)");
   m.def("hj_probe_unique", &hj_probe_unique, "hash join probe, first match");
   m.def("hj_build_chain", &hj_build_chain, "hash join build with chains");
